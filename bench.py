@@ -8,9 +8,13 @@ Multi-GPU (torchrun): each rank draws its own minibatch from its own shard, grad
 averaged with one RCCL all-reduce, every rank applies the same Adam update (weak scaling:
 value = minibatch iterations per second summed over ranks).
 
-Prints ONE JSON line (rank 0).  Also reports the per-phase breakdown, the roofline of the
-dominant kernel (the grouped MFMA GEMM) and the CPU baseline (the oracle, op for op the
-reference's torch-CPU path, timed on this host's cores).
+Prints ONE JSON line (rank 0).  A plain run sets up, warms up, times --steps steps, writes the last
+step's outputs if --dump-outputs DIR is given, and prints the line (the other legs' keys are null).
+--full adds, as runs of their own after the timed loop: the per-phase breakdown, the roofline of
+the dominant kernel (the grouped MFMA GEMM), the CPU baseline (the oracle, op for op the
+reference's torch-CPU path, timed on this host's cores), the M=4096 stress Cholesky, the Kronecker
+mat-vec, the HCP / ECoG training legs, the ELBO and pair-sharded legs and the inference() API path;
+each can still be skipped with its --no-* option.
 """
 import argparse
 import json
@@ -727,6 +731,19 @@ def cpu_baseline(seconds, xs, ys, z):
                       f"D=5, M=256, B=2000 config; mean {1000 * float(np.mean(steady)):.1f} ms/it"}
 
 
+def dump_outputs(out_dir, eng, model):
+    """What the last timed step left for its caller, as float64 .npy files (33 MB at the bench shape):
+      loss_terms  [loss, SELBO_R, KL_W, KL_v, KL_U] of the step's minibatch (eng.out[0:5]);
+      grad        the flat gradient of the 13 parameters (engine.param_layout order);
+      theta       the flat parameter vector after the step's Adam update.
+    The data, the minibatch order, the initial parameters and the Philox noise stream are all seeded, so two
+    runs with the same arguments start from identical inputs."""
+    os.makedirs(out_dir, exist_ok=True)
+    torch.cuda.synchronize()
+    for name, t in (("loss_terms", eng.out[:5]), ("grad", model._grad), ("theta", model._theta)):
+        np.save(os.path.join(out_dir, name + ".npy"), t.detach().to("cpu", torch.float64).numpy())
+
+
 def _relaunch_under_torchrun(n):
     """`python bench.py --gpus N` without a launcher: run the same command under torchrun with N ranks on
     127.0.0.1 as a child process (no exec: the parent has not touched the GPU, and never will)."""
@@ -745,6 +762,12 @@ def main():
     ap.add_argument("--gpus", type=int, default=1)
     ap.add_argument("--steps", type=int, default=300)
     ap.add_argument("--warmup", type=int, default=20)
+    ap.add_argument("--full", action="store_true",
+                    help="after the timed steps also run every other leg (breakdown / roofline, CPU baseline, stress "
+                         "Cholesky, Kronecker mat-vec, HCP / ECoG training, ELBO, pair sharding, API path)")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="write what the last timed step computed (loss terms, gradient, updated parameters) as "
+                         "DIR/<name>.npy")
     ap.add_argument("--cpu-seconds", type=float, default=15.0)
     ap.add_argument("--no-cpu-baseline", action="store_true")
     ap.add_argument("--no-breakdown", action="store_true")
@@ -761,6 +784,10 @@ def main():
     ap.add_argument("--dp-allreduce", choices=["auto", "bucketed", "flat"], default="auto",
                     help="N > 1 gradient all-reduce: flat (auto: DsviTrainer.DP_BUCKET_MIN_BYTES unset) or bucketed + overlapped")
     args = ap.parse_args()
+    if not args.full:
+        # a plain run measures the headline figure only: every other leg is a run of its own behind --full
+        for leg in ("cpu_baseline", "breakdown", "stress", "elbo", "api", "hcp", "ecog", "pair", "kron"):
+            setattr(args, "no_" + leg, True)
 
     # --gpus N is honoured before anything touches the GPU: without a launcher, N > 1 re-runs this
     # script under torchrun as a CHILD process (one rank per GPU) and exits with its status; under a
@@ -863,6 +890,8 @@ def main():
     loss_val = float(eng.out[0])
     ms_per_step = 1000.0 * elapsed / args.steps
     value = world * args.steps / elapsed
+    if args.dump_outputs and rank == 0:
+        dump_outputs(args.dump_outputs, eng, model)
 
     # ---------------------------------------------------------------- per-phase breakdown (eager)
     breakdown, roofline, chol = None, None, None

@@ -10,7 +10,12 @@ GOLDEN = os.path.join(os.path.dirname(os.path.abspath(__file__)), "golden")
 
 
 def load(name):
-    return dict(np.load(os.path.join(GOLDEN, name + ".npz"), allow_pickle=False))
+    """<name>.npz merged with its <name>.part<k>.npz files (make_golden.save splits fixtures near 1 MiB)."""
+    import glob
+    g = {}
+    for path in [os.path.join(GOLDEN, name + ".npz")] + sorted(glob.glob(os.path.join(GOLDEN, name + ".part*.npz"))):
+        g.update(np.load(path, allow_pickle=False))
+    return g
 
 
 def split_lists(g, xkey="x", ykey="y", skey="sizes"):

@@ -13,7 +13,8 @@ from collaborative_nonstationary_multivariate_gaussian_process_amd import distri
 from collaborative_nonstationary_multivariate_gaussian_process_amd import nmgp_dsvi as NM
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-REF_MODEL_PT = "/root/reference/code/notebook/model.pt"
+# the checkpoint the reference ships (code/notebook/model.pt), byte for byte
+REF_MODEL_PT = os.path.join(ROOT, "tests", "golden", "model_pt_shipped.pt")
 
 
 @pytest.mark.parametrize("N,bs", [(200, 200), (10000, 2000), (1003, 128), (37, 5)])
@@ -94,8 +95,6 @@ def test_modelpt_fixture_matches_the_shipped_checkpoint():
     fx = torch.load(os.path.join(ROOT, "tests", "golden", "model_pt.pt"), weights_only=True)
     assert fx["epoch"] == 1999 and float(fx["loss"]) == pytest.approx(151.0889, abs=1e-3)
     assert list(fx["model_state_dict"].keys())[0] == "mu_W" and len(fx["model_state_dict"]) == 13
-    if not os.path.exists(REF_MODEL_PT):
-        pytest.skip("reference tree not present (GPU box); fixture checked in the build container")
     ck = torch.load(REF_MODEL_PT, weights_only=True, map_location="cpu")
     for k, v in ck["model_state_dict"].items():
         assert torch.equal(v, fx["model_state_dict"][k]), k
@@ -144,11 +143,10 @@ def test_driver_data_pickle_loader_refuses_code(tmp_path):
 
 
 def test_driver_data_pickle_loader_reads_reference_toy_pickle():
-    """The reference's shipped simulation pickle (build container only: skipped where the tree is absent)."""
+    """The reference's shipped simulation pickle (data/simulation/sim_illustration_low_freq.pickle, stored
+    byte for byte under tests/golden/)."""
     import os
-    path = "/root/reference/data/simulation/sim_illustration_low_freq.pickle"
-    if not os.path.exists(path):
-        pytest.skip("reference tree not present")
+    path = os.path.join(os.path.dirname(__file__), "golden", "sim_illustration_low_freq.pickle")
     from collaborative_nonstationary_multivariate_gaussian_process_amd.drivers._dataload import load_data_pickle
     obj = load_data_pickle(path)
     assert len(obj) == 4 and all(len(l) == 2 for l in obj)

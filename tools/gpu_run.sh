@@ -5,7 +5,7 @@
 #   quick      tests/test_gpu_primitives.py -k "$QUICK_K" (the round's new kernels first)
 #   suite      the whole -m gpu suite                          -> gpurun_out/<tag>_suite.log
 #   smoke      __graft_entry__.smoke()                          -> gpurun_out/<tag>_smoke.log
-#   bench      default bench.py line                           -> gpurun_out/<tag>_bench.json
+#   bench      the bench.py --full line (every leg)            -> $BENCH_OUT/<tag>_bench.json
 #   prof       rocprofv3 kernel trace + FETCH/WRITE passes of the PM2.5 bench -> gpurun_out/<tag>_pm25_bench_*
 #   pmc        MFMA-busy pass of the PM2.5 step                -> gpurun_out/<tag>_pm25_mfma.json
 #   timeline   PM2.5 step timeline (kernel trace of a graphed run) -> gpurun_out/<tag>_pm25_step_timeline.txt
@@ -20,6 +20,8 @@
 R=${GRAFT_REPO_ROOT:-$(pwd)}
 cd "$R" || exit 1
 mkdir -p gpurun_out
+BENCH_OUT=${BENCH_OUT:-$R/bench_out}   # where the bench step leaves its line (and publish looks for it)
+mkdir -p "$BENCH_OUT"
 TAG=$1; shift
 run() {  # run <name> <cmd...>: the caller's `|| { ...; exit 1; }` stops the script on failure
   local name=$1; shift
@@ -46,9 +48,9 @@ for step in "$@"; do
         || { tail -20 gpurun_out/${TAG}_smoke.log; exit 1; }
       tail -2 gpurun_out/${TAG}_smoke.log ;;
     bench)
-      run bench timeout -k 10 600 python -u bench.py > gpurun_out/${TAG}_bench.json 2> gpurun_out/${TAG}_bench.err \
-        || { tail -20 gpurun_out/${TAG}_bench.err; exit 1; }
-      tail -1 gpurun_out/${TAG}_bench.json | cut -c1-600 ;;
+      run bench timeout -k 10 600 python -u bench.py --full > $BENCH_OUT/${TAG}_bench.json 2> $BENCH_OUT/${TAG}_bench.err \
+        || { tail -20 $BENCH_OUT/${TAG}_bench.err; exit 1; }
+      tail -1 $BENCH_OUT/${TAG}_bench.json | cut -c1-600 ;;
     prof)
       run prof bash tools/profile_bench.sh ${TAG}_pm25_bench > gpurun_out/${TAG}_prof.log 2>&1 \
         || { tail -20 gpurun_out/${TAG}_prof.log; exit 1; } ;;
@@ -91,13 +93,13 @@ for step in "$@"; do
                suite.log smoke.log; do
         [ -f gpurun_out/${TAG}_$f ] && cp gpurun_out/${TAG}_$f profiles/
       done
-      [ -f gpurun_out/${TAG}_bench.json ] && tail -1 gpurun_out/${TAG}_bench.json > profiles/${TAG}_pm25_bench_default.json
+      [ -f $BENCH_OUT/${TAG}_bench.json ] && tail -1 $BENCH_OUT/${TAG}_bench.json > profiles/${TAG}_pm25_bench_default.json
       ls profiles | grep "^${TAG}_" ;;
     n2|n4)
       n=${step#n}
       run $step env NMGP_DIST_BACKEND=gloo timeout -k 10 400 python -m torch.distributed.run --nnodes=1 \
         --nproc-per-node $n --master-addr 127.0.0.1 --master-port 2953$n bench.py --gpus $n --steps 20 --warmup 5 \
-        --no-breakdown --pair-D 32 --elbo-D 32 ${DP_MODE:+--dp-allreduce $DP_MODE} \
+        --full --no-breakdown --pair-D 32 --elbo-D 32 ${DP_MODE:+--dp-allreduce $DP_MODE} \
         > gpurun_out/${TAG}_bench_n${n}_rehearsal.json 2> gpurun_out/${TAG}_bench_n${n}_rehearsal.err \
         || { tail -20 gpurun_out/${TAG}_bench_n${n}_rehearsal.err; exit 1; }
       tail -1 gpurun_out/${TAG}_bench_n${n}_rehearsal.json | cut -c1-600 ;;
