@@ -979,20 +979,37 @@ __device__ inline unsigned long long bits_of(double x) { return __builtin_bit_ca
 __device__ inline unsigned int bits_of(float x) { return __builtin_bit_cast(unsigned int, x); }
 // one element of torch's Adam (lerp form); returns false when grad, exp_avg and exp_avg_sq are all +0
 // (the never-used strictly-upper triangles and unused (i<j) blocks of the factor parameters): the
-// update would leave every value bit-identical, so nothing needs writing
-template <typename T>
+// update would leave every value bit-identical, so nothing needs writing.
+// PINNED spells the fused multiply-adds out.  Left to the compiler's contraction, every 16-byte-vector loop rounds
+// b2 * v and fuses (1 - b2) g * g onto it, while the scalar loops (unaligned pointers, the elements past the last
+// vector) round (1 - b2) g * g and fuse b2 * v, or fuse nothing: last-bit differences between paths of one kernel.
+// The dense kernel (nmgp_adam_*) pins the vector loops' form on all its paths, so an unaligned call equals an
+// aligned one bit for bit and its vector results are what they were.  The lower-triangular kernels keep the
+// unpinned expression: their one or three scalar tail elements are model parameters, and a seeded training run
+// that moved them by an ulp would part from earlier runs of the same seed within a few hundred steps.
+__device__ inline double fma_of(double a, double b, double c) { return __builtin_fma(a, b, c); }
+__device__ inline float fma_of(float a, float b, float c) { return __builtin_fmaf(a, b, c); }
+template <typename T, bool PINNED = false>
 __device__ inline bool adam_elt(T& th, T gi, T& mi, T& vi, T lr, T b1, T b2, T eps, T bc1, T bc2s) {
   if ((bits_of(gi) | bits_of(mi) | bits_of(vi)) == 0) return false;
-  mi = mi + ((T)1 - b1) * (gi - mi);          // exp_avg.lerp_(grad, 1 - beta1)
-  vi = vi * b2 + ((T)1 - b2) * gi * gi;
-  const T denom = dsqrt(vi) / bc2s + eps;
-  th = th - (lr / bc1) * (mi / denom);
+  if constexpr (PINNED) {
+    mi = fma_of((T)1 - b1, gi - mi, mi);
+    const T vb = vi * b2, gs = ((T)1 - b2) * gi;
+    vi = fma_of(gi, gs, vb);
+    const T denom = dsqrt(vi) / bc2s + eps;
+    th = fma_of(-(lr / bc1), mi / denom, th);
+  } else {
+    mi = mi + ((T)1 - b1) * (gi - mi);          // exp_avg.lerp_(grad, 1 - beta1)
+    vi = vi * b2 + ((T)1 - b2) * gi * gi;
+    const T denom = dsqrt(vi) / bc2s + eps;
+    th = th - (lr / bc1) * (mi / denom);
+  }
   return true;
 }
 
 // 16-byte vectors per thread (VEC) when every pointer is 16-byte aligned, grid-strided; the bias
 // corrections are computed once per workgroup (a double pow per element cost more than the memory
-// traffic at HCP's 670 M parameters).  Element arithmetic is unchanged, so results are bit-identical
+// traffic at HCP's 670 M parameters).  Every path uses the pinned form of adam_elt, so results are bit-identical
 // to the scalar form.
 template <typename T, bool VEC>
 __global__ __launch_bounds__(256) void adam_kernel(T* th, const T* g, T* m, T* v, int64_t n, const int64_t* step,
@@ -1021,14 +1038,14 @@ __global__ __launch_bounds__(256) void adam_kernel(T* th, const T* g, T* m, T* v
       if (!any) continue;
       P tq = ((P*)th)[q];
 #pragma unroll
-      for (int e = 0; e < V; ++e) adam_elt<T>(tq.e[e], gq.e[e], mq.e[e], vq.e[e], lr, b1, b2, eps, bc1, bc2s);
+      for (int e = 0; e < V; ++e) adam_elt<T, true>(tq.e[e], gq.e[e], mq.e[e], vq.e[e], lr, b1, b2, eps, bc1, bc2s);
       ((P*)m)[q] = mq;
       ((P*)v)[q] = vq;
       ((P*)th)[q] = tq;
     }
     for (int64_t i = nv * V + tid; i < n; i += stride) {
       T ti = th[i], mi = m[i], vi = v[i];
-      if (adam_elt<T>(ti, g[i], mi, vi, lr, b1, b2, eps, bc1, bc2s)) {
+      if (adam_elt<T, true>(ti, g[i], mi, vi, lr, b1, b2, eps, bc1, bc2s)) {
         m[i] = mi;
         v[i] = vi;
         th[i] = ti;
@@ -1038,7 +1055,7 @@ __global__ __launch_bounds__(256) void adam_kernel(T* th, const T* g, T* m, T* v
     for (int64_t i = tid; i < n; i += stride) {
       T mi = m[i], vi = v[i];
       T ti = th[i];
-      if (adam_elt<T>(ti, g[i], mi, vi, lr, b1, b2, eps, bc1, bc2s)) {
+      if (adam_elt<T, true>(ti, g[i], mi, vi, lr, b1, b2, eps, bc1, bc2s)) {
         m[i] = mi;
         v[i] = vi;
         th[i] = ti;

@@ -530,7 +530,13 @@ int nmgp_adam_lower_advanced_f64(double* theta, const double* grad, double* m, d
 int nmgp_adam_lower_advanced_f32(float* theta, const float* grad, float* m, float* v, int64_t n, const int64_t* tri,
                                  int ntri, int M, const int64_t* step, double lr, double beta1, double beta2,
                                  double eps, hipStream_t stream);
-/* Counter-based Philox4x32-10 standard normals: out[i] = N(0,1) for stream (seed, *counter + i) */
+/* Counter-based Philox4x32-10 standard normals: out[0:n] = the first n elements of the stream with key `seed`
+ * and base = *counter + offset (counter == NULL reads as 0): so (counter = c, offset = o) and (counter = c + o,
+ * offset = 0) are the same stream, and a shorter call is a prefix of a longer one.  Quad t = i / 4 runs Philox
+ * on the counter words (t_lo, t_hi, base_lo, base_hi) with key (seed_lo, seed_hi); its four words c_q give
+ * u_q = (c_q + 0.5) * 2^-32 and, by Box-Muller in float64, out[4t .. 4t+3] = (r0 cos 2 pi u1, r0 sin 2 pi u1,
+ * r1 cos 2 pi u3, r1 sin 2 pi u3), r0 = sqrt(-2 ln u0), r1 = sqrt(-2 ln u2), rounded to the output type.
+ * base does NOT shift the element index: streams of different bases share no quad.               */
 int nmgp_normal_f64(double* out, int64_t n, uint64_t seed, const int64_t* counter, int64_t offset,
                     hipStream_t stream);
 int nmgp_normal_f32(float* out, int64_t n, uint64_t seed, const int64_t* counter, int64_t offset,
