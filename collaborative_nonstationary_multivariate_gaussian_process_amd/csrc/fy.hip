@@ -1,0 +1,283 @@
+// Fused posterior summaries of NMGP.sample_FY (reference code/nmgp_dsvi.py:492-580): per sample s and input n the
+// pair samples -> L, Y = L G + noise, corr = D^-1/2 (L L^T) D^-1/2, accumulated over the samples on the device, so
+// that the (S, N, D, D) correlation tensor is never stored.
+//
+// One workgroup (4 waves) per (input n, slice of samples).  L lives in LDS as its lower-triangular 16 x 16 tiles
+// (tile (ti, tj <= ti) at slot ti (ti + 1) / 2 + tj, 2 KiB each: 72 KiB at D = 128), zero above the diagonal and in
+// the rows past D.  Inside a tile element (r, c) sits at r * 16 + (c ^ ((r >> 1) << 1)): an MFMA operand read (16
+// rows x 2 columns per 32-lane half, 8 bytes each) then touches 32 different 8-byte bank pairs, without padding.
+// cov tile (ti, tj) = sum_{kt <= tj} L(ti, kt) L(tj, kt)^T on v_mfma_f64_16x16x4_f64, tiles above the diagonal of L
+// skipped; the lower-triangular cov tiles are dealt round-robin to the waves, and each wave keeps the running
+// sum and sum of squares of its tiles' correlations in registers across the slice's samples.  The sums leave the
+// workgroup once: straight onto corr_sum / corr_sq when the samples are not sliced (this workgroup owns input n),
+// else into a per-slice workspace that a second kernel adds up in slice order (no floating-point atomics).
+#include "common.hpp"
+
+namespace nmgp {
+
+constexpr int kFyThreads = 256;
+constexpr int kFyWaves = kFyThreads / kWave;
+constexpr int kFyTile = 16;
+constexpr int kFyTileElems = kFyTile * kFyTile;
+constexpr int kFyMaxD = 128;
+constexpr int kFyXcds = 8;
+
+__host__ __device__ inline int fy_ntiles(int nt) { return nt * (nt + 1) / 2; }
+__device__ inline int fy_tile_off(int r, int c) { return r * kFyTile + (c ^ ((r >> 1) << 1)); }
+// Row of element q of a packed lower triangle: the largest i with i (i + 1) / 2 <= q (q <= 8255; the float
+// estimate is off by at most one).
+__device__ inline int fy_tri_row(int q) {
+  int i = (int)((sqrtf((float)(8 * q + 1)) - 1.0f) * 0.5f);
+  i += (i + 1) * (i + 2) / 2 <= q;
+  i -= i * (i + 1) / 2 > q;
+  return i;
+}
+
+// Sample slices: none while the inputs alone fill the chip's 256 CUs, else as many as keep N * slices <= 512.
+static void fy_slicing(int N, int S, int* nsl, int* per) {
+  int want = N >= 256 ? 1 : 512 / N;
+  if (want > S) want = S;
+  if (want < 1) want = 1;
+  *per = (S + want - 1) / want;
+  *nsl = (S + *per - 1) / *per;
+}
+
+template <int NT>
+__global__ __launch_bounds__(kFyThreads) void fy_accum_kernel(
+    const double* __restrict__ pair_mu, const double* __restrict__ pair_sd, int64_t ld_pair,
+    const double* __restrict__ G, const double* __restrict__ z_p, const double* __restrict__ z_f, int64_t z_stride,
+    double sd_err, int D, int N, int S, int per, double* __restrict__ Y, double* __restrict__ corr_sum,
+    double* __restrict__ corr_sq, double* __restrict__ ws, int n_blocks) {
+  constexpr int T = NT * (NT + 1) / 2;                  // lower-triangular tiles
+  constexpr int KMAX = (T + kFyWaves - 1) / kFyWaves;   // cov tiles of one wave
+  extern __shared__ __attribute__((aligned(16))) double fy_smem[];
+  double* Lt = fy_smem;                                 // T tiles
+  double* Gs = Lt + T * kFyTileElems;                   // NT * 16
+  double* Is = Gs + NT * kFyTile;                       // NT * 16: sqrt(1 / cov_ii), 0 past D
+
+  // consecutive inputs share an XCD (and its L2): the (Q, N) operands are read at one n per workgroup, so the 8
+  // inputs of a 64-byte line are best fetched by workgroups behind one L2
+  const int bid = blockIdx.x;
+  const int n = (bid % kFyXcds) * (n_blocks / kFyXcds) + bid / kFyXcds;
+  if (n >= N) return;
+  const int slice = blockIdx.y;
+  const int s0 = slice * per, s1 = min(S, s0 + per);
+  const int tid = threadIdx.x, lane = tid & 63, wave = uniform32(tid >> 6);
+  const int Q = D * (D + 1) / 2;
+
+  for (int e = tid; e < T * kFyTileElems + 2 * NT * kFyTile; e += kFyThreads) fy_smem[e] = 0.0;
+
+  f64x4 sum[KMAX], sq[KMAX];
+#pragma unroll
+  for (int k = 0; k < KMAX; ++k) sum[k] = sq[k] = f64x4{0.0, 0.0, 0.0, 0.0};
+
+  const int ar = lane & 15, ak = lane >> 4;             // MFMA operand row / k of this lane
+  const int frow = tid >> 1, fhalf = tid & 1;           // Y: two threads per row of L, columns of one parity each
+  __syncthreads();
+
+  for (int s = s0; s < s1; ++s) {
+    // ---- pair samples -> L tiles; G column -> LDS
+    const double* zp = z_p + (int64_t)s * z_stride + n;
+    // not unrolled: with 4 or 8 pairs' loads in flight per lane the launch took 20-25 % longer at D = 50 and 128
+    // (each lane's load is a 64-byte line of its own, shared only with the neighbouring inputs' workgroups)
+#pragma unroll 1
+    for (int q = tid; q < Q; q += kFyThreads) {
+      const int i = fy_tri_row(q);
+      const int j = q - i * (i + 1) / 2;
+      const double l = pair_mu[(int64_t)q * ld_pair + n] + pair_sd[(int64_t)q * ld_pair + n] * zp[(int64_t)q * N];
+      Lt[(fy_ntiles(i >> 4) + (j >> 4)) * kFyTileElems + fy_tile_off(i & 15, j & 15)] = i == j ? exp(l) : l;
+    }
+    if (tid < D) Gs[tid] = G[((int64_t)s * D + tid) * N + n];
+    __syncthreads();
+
+    // ---- Y row and the diagonal of cov
+    {
+      double f = 0.0, c = 0.0;
+      if (frow < D) {
+        const int ti = frow >> 4, r = frow & 15;
+        const double* rowt = Lt + fy_ntiles(ti) * kFyTileElems;
+        for (int j = fhalf; j <= frow; j += 2) {
+          const double v = rowt[(j >> 4) * kFyTileElems + fy_tile_off(r, j & 15)];
+          f = fma(v, Gs[j], f);
+          c = fma(v, v, c);
+        }
+      }
+      f += __shfl_xor(f, 1, 64);
+      c += __shfl_xor(c, 1, 64);
+      if (frow < D && fhalf == 0) {
+        const int64_t o = ((int64_t)s * N + n) * D + frow;
+        Y[o] = f + sd_err * z_f[(int64_t)s * z_stride + (int64_t)n * D + frow];
+        Is[frow] = sqrt(1.0 / c);
+      }
+    }
+    __syncthreads();
+
+    // ---- cov tiles on the matrix cores, normalised and accumulated
+    // the tile coordinates are worked out again for every sample (a few scalar operations per tile): hoisted out
+    // of the sample loop, the KMAX tiles' rows, columns and LDS bases stay live together and, at D > 96, no
+    // longer fit the scalar registers
+    int tw = wave;
+    asm volatile("" : "+s"(tw));
+#pragma unroll
+    for (int k = 0; k < KMAX; ++k) {
+      const int t = tw + k * kFyWaves;
+      if (t < T) {
+        const int ti = uniform32(fy_tri_row(t));
+        const int tj = t - fy_ntiles(ti);
+        const double* At = Lt + fy_ntiles(ti) * kFyTileElems;
+        const double* Bt = Lt + fy_ntiles(tj) * kFyTileElems;
+        f64x4 acc = {0.0, 0.0, 0.0, 0.0};
+        for (int kt = 0; kt <= tj; ++kt) {
+#pragma unroll
+          for (int kk = 0; kk < 4; ++kk) {
+            const int o = kt * kFyTileElems + fy_tile_off(ar, kk * 4 + ak);
+            acc = Mfma<double>::mma(At[o], Bt[o], acc);
+          }
+        }
+        const double isj = Is[tj * kFyTile + (lane & 15)];
+#pragma unroll
+        for (int r = 0; r < 4; ++r) {
+          const int row = Mfma<double>::row(lane, r);
+          const double isi = Is[ti * kFyTile + row];
+          // rows or columns past D: Is = 0.  The diagonal is 1, not 1 +- an ulp of rounding noise, which
+          // E[c^2] - mean^2 would turn into a standard deviation of 1e-8 where it is 0 -- unless the
+          // expression is not finite there (cov_ii 0, inf or NaN after an exp under / overflow): that stays.
+          double c = acc[r] * isi * isj;
+          if (ti == tj && row == (lane & 15) && __builtin_isfinite(c)) c = 1.0;
+          sum[k][r] += c;
+          sq[k][r] = fma(c, c, sq[k][r]);
+        }
+      }
+    }
+    __syncthreads();
+  }
+
+  // ---- the slice's sums leave the workgroup: lower triangle held, both triangles written
+  const int64_t dd = (int64_t)D * D;
+  const bool direct = gridDim.y == 1;
+  double* o_sum = direct ? corr_sum + (int64_t)n * dd : ws + (((int64_t)slice * N + n) * 2) * dd;
+  double* o_sq = direct ? corr_sq + (int64_t)n * dd : o_sum + dd;
+#pragma unroll
+  for (int k = 0; k < KMAX; ++k) {
+    const int t = wave + k * kFyWaves;
+    if (t < T) {
+      const int ti = uniform32(fy_tri_row(t));
+      const int tj = t - fy_ntiles(ti);
+      const int j = tj * kFyTile + (lane & 15);
+#pragma unroll
+      for (int r = 0; r < 4; ++r) {
+        const int i = ti * kFyTile + Mfma<double>::row(lane, r);
+        if (i < D && j <= i) {
+          const int64_t a = (int64_t)i * D + j, b = (int64_t)j * D + i;
+          if (direct) {
+            o_sum[a] += sum[k][r];
+            o_sq[a] += sq[k][r];
+            if (j < i) {
+              o_sum[b] += sum[k][r];
+              o_sq[b] += sq[k][r];
+            }
+          } else {
+            o_sum[a] = sum[k][r];
+            o_sq[a] = sq[k][r];
+          }
+        }
+      }
+    }
+  }
+}
+
+// corr_sum / corr_sq += the slices' partial sums, in slice order; one thread per (n, i, j), the partials hold
+// the lower triangle only.
+__global__ __launch_bounds__(256) void fy_reduce_kernel(const double* __restrict__ ws, int nsl, int D, int N,
+                                                         double* __restrict__ corr_sum,
+                                                         double* __restrict__ corr_sq) {
+  const int64_t dd = (int64_t)D * D;
+  const int64_t e = (int64_t)blockIdx.x * 256 + threadIdx.x;
+  if (e >= (int64_t)N * dd) return;
+  const int64_t n = e / dd;
+  const int ij = (int)(e - n * dd), i = ij / D, j = ij - i * D;
+  const int64_t src = (int64_t)max(i, j) * D + min(i, j);
+  double a = 0.0, b = 0.0;
+  for (int sl = 0; sl < nsl; ++sl) {
+    const double* p = ws + (((int64_t)sl * N + n) * 2) * dd + src;
+    a += p[0];
+    b += p[dd];
+  }
+  corr_sum[e] += a;
+  corr_sq[e] += b;
+}
+
+template <int NT>
+static int fy_launch(const double* pair_mu, const double* pair_sd, int64_t ld_pair, const double* G,
+                     const double* z_p, const double* z_f, int64_t z_stride, double sd_err, int D, int N, int S,
+                     int nsl, int per, double* Y, double* corr_sum, double* corr_sq, double* ws, hipStream_t s) {
+  const size_t smem = (size_t)(fy_ntiles(NT) * kFyTileElems + 2 * NT * kFyTile) * sizeof(double);
+  static bool attr_done = false;
+  if (!attr_done) {
+    (void)hipFuncSetAttribute((const void*)fy_accum_kernel<NT>, hipFuncAttributeMaxDynamicSharedMemorySize,
+                              (int)smem);
+    attr_done = true;
+  }
+  const int n_blocks = (N + kFyXcds - 1) / kFyXcds * kFyXcds;
+  hipLaunchKernelGGL(fy_accum_kernel<NT>, dim3((unsigned)n_blocks, (unsigned)nsl), dim3(kFyThreads), smem, s,
+                     pair_mu, pair_sd, ld_pair, G, z_p, z_f, z_stride, sd_err, D, N, S, per, Y, corr_sum, corr_sq, ws,
+                     n_blocks);
+  NMGP_CHECK_LAUNCH();
+  return NMGP_OK;
+}
+
+}  // namespace nmgp
+
+using namespace nmgp;
+
+extern "C" {
+
+int64_t nmgp_fy_workspace_size(int D, int N, int S) {
+  if (D < 1 || D > kFyMaxD || N <= 0 || S <= 0) return 0;
+  int nsl, per;
+  fy_slicing(N, S, &nsl, &per);
+  return nsl == 1 ? 0 : (int64_t)nsl * N * 2 * D * D * (int64_t)sizeof(double);
+}
+
+int nmgp_fy_accum_f64(const double* pair_mu, const double* pair_sd, int64_t ld_pair, const double* G,
+                      const double* z_p, const double* z_f, int64_t z_stride, double sd_err, int D, int N, int S,
+                      double* Y, double* corr_sum, double* corr_sq, void* ws, int64_t ws_bytes, hipStream_t stream) {
+  if (D < 1 || D > kFyMaxD || N < 0 || S < 0) return NMGP_ERR_FY_ARG;
+  if (N == 0 || S == 0) return NMGP_OK;
+  if (!pair_mu || !pair_sd || !G || !z_p || !z_f || !Y || !corr_sum || !corr_sq) return NMGP_ERR_FY_ARG;
+  if (ld_pair < N || z_stride < 0 || N > 0x7fffffff - kFyXcds) return NMGP_ERR_FY_ARG;
+  int nsl, per;
+  fy_slicing(N, S, &nsl, &per);
+  const int64_t need = nmgp_fy_workspace_size(D, N, S);
+  if (need > 0 && (!ws || ws_bytes < need)) return NMGP_ERR_FY_ARG;
+  const int nt = (D + kFyTile - 1) / kFyTile;
+  int rc;
+#define NMGP_FY_CASE(NT_)                                                                                          \
+  case NT_:                                                                                                        \
+    rc = fy_launch<NT_>(pair_mu, pair_sd, ld_pair, G, z_p, z_f, z_stride, sd_err, D, N, S, nsl, per, Y, corr_sum, \
+                        corr_sq, (double*)ws, stream);                                                             \
+    break;
+  switch (nt) {
+    NMGP_FY_CASE(1)
+    NMGP_FY_CASE(2)
+    NMGP_FY_CASE(3)
+    NMGP_FY_CASE(4)
+    NMGP_FY_CASE(5)
+    NMGP_FY_CASE(6)
+    NMGP_FY_CASE(7)
+    NMGP_FY_CASE(8)
+    default:
+      return NMGP_ERR_FY_ARG;
+  }
+#undef NMGP_FY_CASE
+  if (rc != NMGP_OK) return rc;
+  if (nsl > 1) {
+    const int64_t total = (int64_t)N * D * D;
+    hipLaunchKernelGGL(fy_reduce_kernel, dim3((unsigned)((total + 255) / 256)), dim3(256), 0, stream,
+                       (const double*)ws, nsl, D, N, corr_sum, corr_sq);
+    NMGP_CHECK_LAUNCH();
+  }
+  return NMGP_OK;
+}
+
+}  // extern "C"

@@ -1118,5 +1118,42 @@ def normal_(out, seed, counter=None, offset=0):
     return out
 
 
+def fy_workspace(D, N, S, device):
+    """Workspace of fy_accum_ for chunks of up to S samples (the slices' partial sums), or None when the samples
+    are not sliced (N >= 256 or S == 1)."""
+    # a shorter last chunk can be cut into more slices than a full one: at most min(S, 512 // N), one sample each
+    need = max(L.lib().nmgp_fy_workspace_size(D, N, s) for s in {S, min(S, max(1, 512 // max(N, 1)))})
+    return torch.empty(need, dtype=torch.uint8, device=device) if need > 0 else None
+
+
+def fy_accum_(pair_mu, pair_sd, G, z_p, z_f, sd_err, Y, corr_sum, corr_sq, ws=None):
+    """One chunk of the fused sample_FY summaries (csrc/fy.hip): Y (S, N, D) is written, corr_sum / corr_sq
+    (N, D, D) are accumulated onto.  pair_mu / pair_sd (Q, N) may have a row stride; G (S, D, N) is contiguous;
+    z_p (S, >= Q N) and z_f (S, >= N D) are column ranges of one noise block (same row stride, unit column
+    stride).  ws: fy_workspace(...) kept by a caller that runs several chunks, else allocated here."""
+    for name, t in (("pair_mu", pair_mu), ("pair_sd", pair_sd), ("G", G), ("z_p", z_p), ("z_f", z_f), ("Y", Y),
+                    ("corr_sum", corr_sum), ("corr_sq", corr_sq)):
+        L.require_device(t, name)
+        assert t.dtype == torch.float64, name
+    S, D, N = G.shape
+    assert G.is_contiguous() and Y.is_contiguous() and corr_sum.is_contiguous() and corr_sq.is_contiguous()
+    assert pair_mu.shape == pair_sd.shape == (D * (D + 1) // 2, N)
+    assert pair_mu.stride(1) == 1 and pair_sd.stride(1) == 1 and pair_mu.stride(0) == pair_sd.stride(0) >= N
+    assert Y.shape == (S, N, D) and corr_sum.shape == corr_sq.shape == (N, D, D)
+    Q = D * (D + 1) // 2
+    assert z_p.dim() == z_f.dim() == 2 and z_p.shape[0] == z_f.shape[0] == S
+    assert z_p.shape[1] >= Q * N and z_f.shape[1] >= N * D
+    assert S == 1 or z_p.stride(0) == z_f.stride(0)
+    assert (z_p.stride(1) == 1 or z_p.shape[1] == 1) and (z_f.stride(1) == 1 or z_f.shape[1] == 1)
+    z_stride = z_p.stride(0) if S > 1 else 0
+    lib = L.lib()
+    need = lib.nmgp_fy_workspace_size(D, N, S)
+    if need > 0 and (ws is None or ws.numel() * ws.element_size() < need):
+        ws = torch.empty(need, dtype=torch.uint8, device=G.device)                      # slices' partial sums
+    L.check(lib.nmgp_fy_accum_f64(L.ptr(pair_mu), L.ptr(pair_sd), pair_mu.stride(0), L.ptr(G), L.ptr(z_p), L.ptr(z_f),
+                                  int(z_stride), float(sd_err), D, N, S, L.ptr(Y), L.ptr(corr_sum), L.ptr(corr_sq),
+                                  L.ptr(ws) if need > 0 else None, need, L.stream_handle()), "fy_accum")
+
+
 def counter_add_(counter, inc):
     L.check(L.lib().nmgp_counter_add(ctypes.c_void_p(counter.data_ptr()), int(inc), L.stream_handle()), "counter")

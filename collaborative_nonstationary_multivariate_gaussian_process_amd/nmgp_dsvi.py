@@ -1043,6 +1043,15 @@ def sample_FY(model, x, n_sample=1000):
     return tuple(o.cpu().numpy() for o in out)
 
 
+def summarize_FY(model, x, n_sample=1000, quantiles=(0.025, 0.975)):
+    """What the reference's drivers make of sample_FY (NMGP_ECoG_full.py:329-332): means and quantile bands of
+    tilde_ell and Y, mean and sd of the output correlations -- a dict of numpy arrays (predict.summarize_FY; the
+    (S, N, D, D) correlation samples are never stored)."""
+    from . import predict
+    out = predict.summarize_FY(model, torch.from_numpy(np.asarray(x)).to(F64), n_sample=n_sample, quantiles=quantiles)
+    return {k: v.cpu().numpy() for k, v in out.items()}
+
+
 def predict_Y(model, X_list):
     """code/nmgp_dsvi.py:927-930 (numpy output)."""
     X_list = [torch.from_numpy(np.asarray(x)).to(F64) for x in X_list]

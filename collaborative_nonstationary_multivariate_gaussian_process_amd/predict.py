@@ -226,26 +226,22 @@ def _sampling_setup(model, x):
     return st
 
 
-def _sample_chunk(st, zc, fy):
-    """S samples from their noise block zc (S, per-sample noise).  Returns t (S,N), Lfull (S,D,D,N),
-    G (S,D,N) and the F-noise (S, N) or (S, N, D)."""
+def _sample_TG(st, zc):
+    """The part of a chunk that sample_Y, sample_FY and summarize_FY share: tilde-ell T (S, N) and the latent
+    G (S, D, N) of S samples from their noise block zc (S, per-sample noise, laid out [z_v M][z_t N][z_p Q N]
+    [z_g D N][z_f ...]).  Also returns the column offsets of z_p and z_f in zc."""
     N, D, M = st["N"], st["D"], st["M"]
     Q = len(st["pairs"])
     S = zc.shape[0]
     o = 0
     z_v = zc[:, o:o + M]; o += M
     z_t = zc[:, o:o + N]; o += N
-    z_p = zc[:, o:o + Q * N].reshape(S, Q, N); o += Q * N
+    o_p = o; o += Q * N
     z_g = zc[:, o:o + D * N].reshape(S, D, N); o += D * N
-    z_f = zc[:, o:].reshape(S, N, D) if fy else zc[:, o:o + N]
+    o_f = o
     # v = mu_v + chol(Sigma_v + 1e-4 I) z_v ; t = P_t v + sqrt(var_t + 1e-4) z_t   (JGP_S)
     V = st["mu_v"].reshape(1, M) + H.matmul(z_v.contiguous(), st["Cv"], transB=True, maskB=L.B_UPPER)
     T = H.matmul(V, st["Pt"], transB=True) + torch.sqrt(st["var_t"] + JIT).reshape(1, N) * z_t
-    # pair samples (S, Q, N); the diagonal pairs are log L_ii
-    Ls = st["pair_mu"].unsqueeze(0) + st["pair_sd"].unsqueeze(0) * z_p
-    Lfull = torch.zeros(S, D, D, N, dtype=F64, device=V.device)
-    for q, (i, j) in enumerate(st["pairs"]):
-        Lfull[:, i, j] = torch.exp(Ls[:, q]) if i == j else Ls[:, q]
     # G | ell  (MGP_d with the sample's Gibbs kernel; code/nmgp_dsvi.py:468-472)
     ellZ, ellX = torch.exp(V), torch.exp(T)
     KG12 = torch.empty(S, N, M, dtype=F64, device=V.device)
@@ -267,6 +263,23 @@ def _sample_chunk(st, zc, fy):
         PL = H.bmm(PG, st["lW"][d], maskB=L.B_LOWER)
         var_g[:, d] = var0 + (PL * PL).sum(2)
     G = mu_g.transpose(1, 2) + torch.sqrt(var_g + JIT) * z_g           # (S, D, N)
+    return T, G, o_p, o_f
+
+
+def _sample_chunk(st, zc, fy):
+    """S samples from their noise block zc (S, per-sample noise).  Returns t (S,N), Lfull (S,D,D,N),
+    G (S,D,N) and the F-noise (S, N) or (S, N, D)."""
+    N, D = st["N"], st["D"]
+    Q = len(st["pairs"])
+    S = zc.shape[0]
+    T, G, o_p, o_f = _sample_TG(st, zc)
+    z_p = zc[:, o_p:o_p + Q * N].reshape(S, Q, N)
+    z_f = zc[:, o_f:].reshape(S, N, D) if fy else zc[:, o_f:o_f + N]
+    # pair samples (S, Q, N); the diagonal pairs are log L_ii
+    Ls = st["pair_mu"].unsqueeze(0) + st["pair_sd"].unsqueeze(0) * z_p
+    Lfull = torch.zeros(S, D, D, N, dtype=F64, device=T.device)
+    for q, (i, j) in enumerate(st["pairs"]):
+        Lfull[:, i, j] = torch.exp(Ls[:, q]) if i == j else Ls[:, q]
     return T, Lfull, G, z_f
 
 
@@ -322,3 +335,64 @@ def sample_FY(model, x, n_sample=1000, noise_tape=None):
         Ts.append(T), Ys.append(F + sd_err * z_f), Cs.append(torch.matmul(torch.matmul(invstd, cov), invstd))
         done += S
     return torch.cat(Ts), torch.cat(Ys), torch.cat(Cs)
+
+
+def _quantiles_dim0(t, qs):
+    """np.quantile(t, qs, axis=0) (linear interpolation between the order statistics) by a sort along dim 0:
+    torch.quantile refuses inputs above 16 M elements."""
+    S = t.shape[0]
+    srt = torch.sort(t, dim=0).values
+    out = []
+    for q in qs:
+        pos = float(q) * (S - 1)
+        lo = min(max(int(np.floor(pos)), 0), S - 1)
+        hi = min(lo + 1, S - 1)
+        out.append(torch.lerp(srt[lo], srt[hi], pos - lo))
+    return torch.stack(out)
+
+
+def summarize_FY(model, x, n_sample=1000, quantiles=(0.025, 0.975), noise_tape=None, keep_samples=False):
+    """What the reference's drivers keep of NMGP.sample_FY (code/nmgp_dsvi.py:492-580; NMGP_ECoG_full.py:329-332):
+    means and quantile bands of tilde_ell and Y, mean and population sd of the output correlations, as a dict of
+    device tensors.  Same setup, chunking, noise layout and stream as sample_FY; each chunk's tail (pair samples,
+    L, Y, L L^T, normalisation, accumulation over the samples) is one fused launch (csrc/fy.hip), so only
+    O(S N D + N D^2) is ever stored -- the (S, N, D, D) correlation samples are not.  keep_samples=True adds
+    Ys (S, N, D) and tilde_ells (S, N)."""
+    qs = [float(q) for q in quantiles]
+    if any(not 0.0 <= q <= 1.0 for q in qs):
+        raise ValueError("quantiles must lie in [0, 1]")
+    n_sample = int(n_sample)
+    if n_sample < 1:
+        raise ValueError("n_sample must be at least 1")
+    dev = model.device_
+    x = torch.as_tensor(x).reshape(-1, 1).to(F64).to(dev).contiguous()
+    st = _sampling_setup(model, x)
+    N, D, M = st["N"], st["D"], st["M"]
+    if D > 128:
+        raise ValueError("summarize_FY: the fused kernel holds L in one workgroup's LDS, D <= 128")
+    Q = len(st["pairs"])
+    per = M + N + Q * N + D * N + N * D
+    draws = _Draws(dev, noise_tape)
+    sd_err = (st["s2_err"] + JIT) ** 0.5
+    Ts = torch.empty(n_sample, N, dtype=F64, device=dev)
+    Ys = torch.empty(n_sample, N, D, dtype=F64, device=dev)
+    csum = torch.zeros(N, D, D, dtype=F64, device=dev)
+    csq = torch.zeros(N, D, D, dtype=F64, device=dev)
+    chunk = _chunk_size(n_sample, N, M)
+    ws = H.fy_workspace(D, N, chunk, dev)
+    done = 0
+    while done < n_sample:
+        S = min(chunk, n_sample - done)
+        zc = draws.take(S, per)
+        T, G, o_p, o_f = _sample_TG(st, zc)
+        Ts[done:done + S] = T
+        H.fy_accum_(st["pair_mu"], st["pair_sd"], G.contiguous(), zc[:, o_p:], zc[:, o_f:], sd_err,
+                    Ys[done:done + S], csum, csq, ws=ws)
+        done += S
+    mean = csum / n_sample
+    out = {"tilde_ell_mean": Ts.mean(0), "tilde_ell_quantiles": _quantiles_dim0(Ts, qs),
+           "Y_mean": Ys.mean(0), "Y_quantiles": _quantiles_dim0(Ys, qs),
+           "corr_mean": mean, "corr_sd": torch.sqrt(torch.clamp(csq / n_sample - mean * mean, min=0.0))}
+    if keep_samples:
+        out["Ys"], out["tilde_ells"] = Ys, Ts
+    return out

@@ -631,6 +631,29 @@ int nmgp_batch_gather_f32(const float* Xb, const float* Yb, const int32_t* Ib, c
                           int64_t nseg, int64_t nbatch, int64_t* batch_counter, float* x, float* y,
                           int32_t* row_out, int32_t* seg, hipStream_t stream);
 
+/* Fused posterior summaries of NMGP.sample_FY (code/nmgp_dsvi.py:492-580, whose (S, N, D, D) correlation tensor the
+ * reference's drivers only ever average, NMGP_ECoG_full.py:329-332).  fp64.  For every sample s < S and input n < N,
+ * with q running over the pairs (i, j <= i) in row order (q = i (i + 1) / 2 + j):
+ *   l_q = pair_mu[q * ld_pair + n] + pair_sd[q * ld_pair + n] * z_p[s * z_stride + q * N + n],
+ *   L_ii = exp(l), L_ij = l (j < i);
+ *   Y[(s * N + n) * D + i] = sum_{j <= i} L_ij G[(s * D + j) * N + n] + sd_err * z_f[s * z_stride + n * D + i];
+ *   cov = L L^T (v_mfma_f64_16x16x4_f64), corr_ij = cov_ij * sqrt(1 / cov_ii) * sqrt(1 / cov_jj)  (:567-569),
+ *   corr_ii = 1 exactly where the expression is finite (its rounding noise on the diagonal would show as 1e-8 in
+ *   the sd); where cov_ii is 0, inf or NaN the expression's NaN is kept;
+ *   corr_sum[(n * D + i) * D + j] += corr_ij, corr_sq[...] += corr_ij^2   (full symmetric D x D).
+ * corr_sum / corr_sq ACCUMULATE (the caller zeroes them once; the chunks of one summary add up); Y is overwritten.
+ * z_p and z_f point into one noise block with a per-sample stride of z_stride elements.  When N alone cannot fill
+ * the chip the samples are cut into slices whose partial sums go through `ws` (nmgp_fy_workspace_size bytes, 0 when
+ * unsliced) and are added in slice order: no floating-point atomics, the same call gives the same bits.  All
+ * indexing is 64-bit.  Returns 0 (nothing launched when S == 0 or N == 0), NMGP_ERR_FY_ARG when D is outside
+ * 1..128, S or N is negative, a pointer is NULL, ld_pair < N, or the workspace is missing / too small; nothing is
+ * launched then either.                                                                                          */
+#define NMGP_ERR_FY_ARG (-60)
+int64_t nmgp_fy_workspace_size(int D, int N, int S);
+int nmgp_fy_accum_f64(const double* pair_mu, const double* pair_sd, int64_t ld_pair, const double* G,
+                      const double* z_p, const double* z_f, int64_t z_stride, double sd_err, int D, int N, int S,
+                      double* Y, double* corr_sum, double* corr_sq, void* ws, int64_t ws_bytes, hipStream_t stream);
+
 /* Whole-step HIP graphs (the reference runs its step eagerly, code/nmgp_dsvi.py:829-854; the build captures
  * noise -> forward -> backward -> Adam once and replays it).  Capture goes straight through the HIP runtime:
  * begin on `stream` (thread-local mode; other streams join through event waits and must join back before
