@@ -225,6 +225,9 @@ _SIGS = {
     "nmgp_fy_workspace_size": (c_i64, [c_int, c_int, c_int]),
     "nmgp_fy_accum_f64": (c_int, [c_vp, c_vp, c_i64, c_vp, c_vp, c_vp, c_i64, c_dbl, c_int, c_int, c_int, c_vp, c_vp,
                                   c_vp, c_vp, c_i64, c_vp]),
+    "nmgp_y_workspace_size": (c_i64, [c_int, c_int, c_int]),
+    "nmgp_y_accum_f64": (c_int, [c_vp, c_vp, c_i64, c_vp, c_vp, c_vp, c_i64, c_vp, c_vp, c_dbl, c_int, c_int, c_int,
+                                 c_vp, c_vp, c_vp, c_vp, c_vp, c_vp, c_vp, c_vp, c_vp, c_vp, c_vp, c_i64, c_vp]),
     "nmgp_counter_add": (c_int, [c_vp, c_i64, c_vp]),
     "nmgp_pbar_reduce_f64": (c_int, [c_vp, c_i64, c_vp, c_i64, c_vp, c_int, c_int, c_int, c_vp]),
     "nmgp_pbar_reduce_f32": (c_int, [c_vp, c_i64, c_vp, c_i64, c_vp, c_int, c_int, c_int, c_vp]),

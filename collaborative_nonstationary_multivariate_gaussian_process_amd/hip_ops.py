@@ -1155,5 +1155,58 @@ def fy_accum_(pair_mu, pair_sd, G, z_p, z_f, sd_err, Y, corr_sum, corr_sq, ws=No
                                   L.ptr(ws) if need > 0 else None, need, L.stream_handle()), "fy_accum")
 
 
+def y_workspace(D, N, S, device):
+    """Workspace of y_accum_ for chunks of up to S samples (the sample slices' partial sums), or None when the
+    samples are not sliced.  The size does not decrease with S, so a shorter last chunk fits."""
+    need = L.lib().nmgp_y_workspace_size(D, N, S)
+    return torch.empty(need, dtype=torch.uint8, device=device) if need > 0 else None
+
+
+def y_accum_(pair_mu, pair_sd, G, z_p, z_f, I, sd_err, Y, F, F_sum, F_sq, L_sum, L_sq, G_sum, G_sq, y=None,
+             lse_max=None, lse_sum=None, ws=None):
+    """One chunk of the fused sample_Y summaries (csrc/ysum.hip): Y and F (S, N) are written; F_sum / F_sq (N),
+    L_sum / L_sq (N, D), G_sum / G_sq (D, N) and, with observations y (N), the running log-sum-exp state
+    lse_max / lse_sum (N) are accumulated onto.  pair_mu / pair_sd (Q, N) may have a row stride; G (S, D, N) is
+    contiguous; I (N) int64 output ids; z_p (S, >= Q N) and z_f (S, >= N) are column ranges of one noise block
+    (same row stride, unit column stride).  ws: y_workspace(...) kept by a caller that runs several chunks, else
+    allocated here."""
+    named = [("pair_mu", pair_mu), ("pair_sd", pair_sd), ("G", G), ("z_p", z_p), ("z_f", z_f), ("Y", Y), ("F", F),
+             ("F_sum", F_sum), ("F_sq", F_sq), ("L_sum", L_sum), ("L_sq", L_sq), ("G_sum", G_sum), ("G_sq", G_sq)]
+    if y is not None:
+        assert lse_max is not None and lse_sum is not None, "y needs the lse_max / lse_sum state"
+        named += [("y", y), ("lse_max", lse_max), ("lse_sum", lse_sum)]
+    for name, t in named:
+        L.require_device(t, name)
+        assert t.dtype == torch.float64, name
+    L.require_device(I, "I")
+    assert I.dtype == torch.int64 and I.is_contiguous()
+    S, D, N = G.shape
+    Q = D * (D + 1) // 2
+    assert I.shape == (N,)
+    assert G.is_contiguous() and all(t.is_contiguous() for _, t in named[5:])
+    assert pair_mu.shape == pair_sd.shape == (Q, N)
+    assert pair_mu.stride(1) == 1 and pair_sd.stride(1) == 1 and pair_mu.stride(0) == pair_sd.stride(0) >= N
+    assert Y.shape == F.shape == (S, N) and F_sum.shape == F_sq.shape == (N,)
+    assert L_sum.shape == L_sq.shape == (N, D) and G_sum.shape == G_sq.shape == (D, N)
+    if y is not None:
+        assert y.shape == lse_max.shape == lse_sum.shape == (N,)
+    assert z_p.dim() == z_f.dim() == 2 and z_p.shape[0] == z_f.shape[0] == S
+    assert z_p.shape[1] >= Q * N and z_f.shape[1] >= N
+    assert S == 1 or z_p.stride(0) == z_f.stride(0)
+    assert (z_p.stride(1) == 1 or z_p.shape[1] == 1) and (z_f.stride(1) == 1 or z_f.shape[1] == 1)
+    z_stride = z_p.stride(0) if S > 1 else 0
+    lib = L.lib()
+    need = lib.nmgp_y_workspace_size(D, N, S)
+    if need > 0 and (ws is None or ws.numel() * ws.element_size() < need):
+        ws = torch.empty(need, dtype=torch.uint8, device=G.device)                      # slices' partial sums
+    L.check(lib.nmgp_y_accum_f64(L.ptr(pair_mu), L.ptr(pair_sd), pair_mu.stride(0), L.ptr(G), L.ptr(z_p), L.ptr(z_f),
+                                 int(z_stride), L.ptr(I), L.ptr(y), float(sd_err), D, N, S, L.ptr(Y), L.ptr(F),
+                                 L.ptr(F_sum), L.ptr(F_sq), L.ptr(L_sum), L.ptr(L_sq), L.ptr(G_sum), L.ptr(G_sq),
+                                 L.ptr(lse_max) if y is not None else None,
+                                 L.ptr(lse_sum) if y is not None else None,
+                                 L.ptr(ws) if need > 0 else None, ws.numel() * ws.element_size() if need > 0 else 0,
+                                 L.stream_handle()), "y_accum")
+
+
 def counter_add_(counter, inc):
     L.check(L.lib().nmgp_counter_add(ctypes.c_void_p(counter.data_ptr()), int(inc), L.stream_handle()), "counter")

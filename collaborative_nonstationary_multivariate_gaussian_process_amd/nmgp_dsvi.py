@@ -1052,6 +1052,17 @@ def summarize_FY(model, x, n_sample=1000, quantiles=(0.025, 0.975)):
     return {k: v.cpu().numpy() for k, v in out.items()}
 
 
+def summarize_Y(model, X_list, Y_list=None, n_sample=1000, index=None, quantiles=(0.025, 0.975)):
+    """What the reference's drivers make of sample_Y on held-out rows (NMGP_ECoG_pred.py:277-299): means, sds and
+    quantile bands per row and, with the observations Y_list, log predictive density, RMSE and coverage -- a dict
+    of numpy arrays (predict.summarize_Y; the (S, D, D, N) pair tensor of sample_Y is never built)."""
+    from . import predict
+    to = lambda lst: [torch.from_numpy(np.asarray(a)).to(F64) for a in lst]
+    out = predict.summarize_Y(model, to(X_list), None if Y_list is None else to(Y_list), n_sample=n_sample,
+                              index=index, quantiles=quantiles)
+    return {k: v.cpu().numpy() for k, v in out.items()}
+
+
 def predict_Y(model, X_list):
     """code/nmgp_dsvi.py:927-930 (numpy output)."""
     X_list = [torch.from_numpy(np.asarray(x)).to(F64) for x in X_list]

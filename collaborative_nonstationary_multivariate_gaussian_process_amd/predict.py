@@ -396,3 +396,96 @@ def summarize_FY(model, x, n_sample=1000, quantiles=(0.025, 0.975), noise_tape=N
     if keep_samples:
         out["Ys"], out["tilde_ells"] = Ys, Ts
     return out
+
+
+def _pop_sd(sq_mean, mean):
+    return torch.sqrt(torch.clamp(sq_mean - mean * mean, min=0.0))
+
+
+def summarize_Y(model, X_list, Y_list=None, n_sample=1000, index=None, quantiles=(0.025, 0.975), noise_tape=None,
+                keep_samples=False):
+    """What the reference's drivers keep of NMGP.sample_Y on held-out rows (code/nmgp_dsvi.py:406-490;
+    NMGP_ECoG_pred.py:277-299): mean, population sd and quantile bands of Y, mean and sd of the noise-free F, of
+    row I_n of L and of G, mean and bands of tilde_ell -- and, when the observations Y_list are given, the scores:
+    log predictive density lpd (N,) = log mean_s N(y_n | F_sn, sigma2_err + 1e-4) and its mean, RMSE of F_mean,
+    coverage of the outermost requested Y band and the number of scored rows, per list entry (rows whose y is
+    not finite are left out of every score and keep a NaN lpd).  A dict of device tensors.  Same setup, chunking,
+    noise layout and stream as sample_Y; each chunk's tail is one fused call (csrc/ysum.hip) that reads only the
+    I_n + 1 pairs of row n, so O(S N + N D) is stored and the (S, D, D, N) tensor of sample_Y is not.
+    keep_samples=True adds Ys, Fs and tilde_ells, each (S, N)."""
+    qs = [float(q) for q in quantiles]
+    if any(not 0.0 <= q <= 1.0 for q in qs):
+        raise ValueError("quantiles must lie in [0, 1]")
+    n_sample = int(n_sample)
+    if n_sample < 1:
+        raise ValueError("n_sample must be at least 1")
+    D = model.D
+    ids = list(range(len(X_list))) if index is None else [int(j) for j in index]
+    if len(ids) != len(X_list):
+        raise ValueError("index needs one output id per entry of X_list")
+    if any(not 0 <= j < D for j in ids):
+        raise ValueError(f"output ids must lie in 0..{D - 1}")
+    xs = [torch.as_tensor(x).reshape(-1).to(F64) for x in X_list]
+    sizes = [int(x.shape[0]) for x in xs]
+    ys = None
+    if Y_list is not None:
+        ys = [torch.as_tensor(y).reshape(-1).to(F64) for y in Y_list]
+        if len(ys) != len(xs) or any(y.shape[0] != n for y, n in zip(ys, sizes)):
+            raise ValueError("Y_list must match X_list entry by entry")
+    dev = model.device_
+    I = torch.cat([torch.full((n,), j, dtype=torch.long) for n, j in zip(sizes, ids)]).to(dev)
+    x = torch.cat(xs).to(dev).reshape(-1, 1).contiguous()
+    st = _sampling_setup(model, x)
+    N, M = st["N"], st["M"]
+    Q = len(st["pairs"])
+    per = M + N + Q * N + D * N + N
+    draws = _Draws(dev, noise_tape)
+    sd_err = (st["s2_err"] + JIT) ** 0.5
+    z = lambda *shape: torch.zeros(*shape, dtype=F64, device=dev)
+    Ts, Ys, Fs = (torch.empty(n_sample, N, dtype=F64, device=dev) for _ in range(3))
+    F_sum, F_sq, L_sum, L_sq, G_sum, G_sq = z(N), z(N), z(N, D), z(N, D), z(D, N), z(D, N)
+    y = lse_max = lse_sum = None
+    if ys is not None:
+        y = torch.cat(ys).to(dev)
+        lse_max, lse_sum = torch.full((N,), float("-inf"), dtype=F64, device=dev), z(N)
+    chunk = _chunk_size(n_sample, N, M)
+    ws = H.y_workspace(D, N, chunk, dev)
+    done = 0
+    while done < n_sample:
+        S = min(chunk, n_sample - done)
+        zc = draws.take(S, per)
+        T, G, o_p, o_f = _sample_TG(st, zc)
+        Ts[done:done + S] = T
+        H.y_accum_(st["pair_mu"], st["pair_sd"], G.contiguous(), zc[:, o_p:], zc[:, o_f:], I, sd_err,
+                   Ys[done:done + S], Fs[done:done + S], F_sum, F_sq, L_sum, L_sq, G_sum, G_sq, y=y,
+                   lse_max=lse_max, lse_sum=lse_sum, ws=ws)
+        done += S
+    Y_mean, F_mean, L_mean, G_mean = Ys.mean(0), F_sum / n_sample, L_sum / n_sample, G_sum / n_sample
+    Yq = _quantiles_dim0(Ys, qs)
+    out = {"Y_mean": Y_mean, "Y_sd": _pop_sd((Ys * Ys).mean(0), Y_mean), "Y_quantiles": Yq,
+           "F_mean": F_mean, "F_sd": _pop_sd(F_sq / n_sample, F_mean),
+           "tilde_ell_mean": Ts.mean(0), "tilde_ell_quantiles": _quantiles_dim0(Ts, qs),
+           "L_mean": L_mean, "L_sd": _pop_sd(L_sq / n_sample, L_mean),
+           "G_mean": G_mean, "G_sd": _pop_sd(G_sq / n_sample, G_mean)}
+    if y is not None:
+        ok = torch.isfinite(y)
+        nan = torch.full((), float("nan"), dtype=F64, device=dev)
+        lpd = torch.where(ok, lse_max + torch.log(lse_sum) - float(np.log(n_sample)), nan)
+
+        def mean_of(v, mask):
+            return torch.where(mask, v, torch.zeros_like(v)).sum() / mask.sum()          # 0 / 0 = NaN: none scored
+
+        err2 = (F_mean - y) ** 2
+        out["lpd"], out["mean_lpd"] = lpd, mean_of(lpd, ok)
+        out["rmse_all"] = torch.sqrt(mean_of(err2, ok))
+        bounds = np.cumsum([0] + sizes)
+        parts = [slice(int(a), int(b)) for a, b in zip(bounds[:-1], bounds[1:])]
+        out["rmse"] = torch.stack([torch.sqrt(mean_of(err2[p], ok[p])) for p in parts])
+        out["n_scored"] = torch.stack([ok[p].sum() for p in parts])
+        if len(qs) >= 2:
+            lo, hi = Yq[int(np.argmin(qs))], Yq[int(np.argmax(qs))]
+            inside = ((y >= lo) & (y <= hi)).to(F64)
+            out["coverage"] = torch.stack([mean_of(inside[p], ok[p]) for p in parts])
+    if keep_samples:
+        out["Ys"], out["Fs"], out["tilde_ells"] = Ys, Fs, Ts
+    return out

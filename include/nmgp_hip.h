@@ -654,6 +654,37 @@ int nmgp_fy_accum_f64(const double* pair_mu, const double* pair_sd, int64_t ld_p
                       const double* z_p, const double* z_f, int64_t z_stride, double sd_err, int D, int N, int S,
                       double* Y, double* corr_sum, double* corr_sq, void* ws, int64_t ws_bytes, hipStream_t stream);
 
+/* Fused held-out summaries of NMGP.sample_Y (code/nmgp_dsvi.py:406-490; the drivers keep a mean curve, a band and an
+ * RMSE of its samples, NMGP_ECoG_pred.py:277-299).  fp64.  Input n belongs to output i = I[n]; for every sample
+ * s < S and input n < N, with j = 0..i in ascending order and q = i (i + 1) / 2 + j:
+ *   l_j = fma(pair_sd[q * ld_pair + n], z_p[s * z_stride + q * N + n], pair_mu[q * ld_pair + n]),  l_i = exp(l_i);
+ *   F[s * N + n] = sum_j l_j G[(s * D + j) * N + n]   (one fma per j, chained in j order);
+ *   Y[s * N + n] = F + sd_err * z_f[s * z_stride + n];
+ *   F_sum[n] += F, F_sq[n] += F^2;  L_sum[n * D + j] += l_j, L_sq[...] += l_j^2 for j <= i (row I_n of L; the
+ *   columns j > i are not touched);  G_sum[j * N + n] += G, G_sq[...] += G^2 for every j < D;
+ *   with y: a = -0.5 log(2 pi v) - (y[n] - F)^2 / (2 v), v = sd_err^2, folded into the running log-sum-exp
+ *   (lse_max[n], lse_sum[n]) -- log sum_s exp(a_s) = lse_max + log(lse_sum) -- by M = max(m1, m2),
+ *   r = r1 exp(m1 - M) + r2 exp(m2 - M); the caller starts it at (-inf, 0), two empty states stay (-inf, 0), a NaN
+ *   y[n] makes both words NaN at that n only, y[n] = +-inf leaves the state as it was.
+ * Only the I_n + 1 pairs of row I_n are read at input n; no (S, D, D, N) tensor exists.  The sums and the
+ * log-sum-exp state ACCUMULATE over calls (the caller initialises them once), in sample order; Y and F are
+ * overwritten.  y may be NULL: lse_max / lse_sum are then neither required nor touched.  An I[n] outside 0..D-1
+ * indexes nothing: Y, F, F_sum, F_sq, the whole row n of L_sum / L_sq and the log-sum-exp state get NaN at that n
+ * (G_sum / G_sq do not depend on I).  z_p and z_f point into one noise block with a per-sample stride of z_stride
+ * elements.  When ceil(N / 64) (D + 1) waves cannot fill the chip the samples are cut into slices whose sums go
+ * through `ws` (nmgp_y_workspace_size bytes, 0 when unsliced, non-decreasing in S) and are added in slice order:
+ * no floating-point atomics, the same call gives the same bits.  All indexing is 64-bit.  Returns 0 (nothing
+ * launched when S == 0 or N == 0), NMGP_ERR_Y_ARG when D < 1, S or N is negative, a required pointer is NULL
+ * (lse_max / lse_sum count when y is given), ld_pair < N, z_stride < 0, S > 262140 or D > 262139 (grid limits), or
+ * the workspace is missing / too small; nothing is launched then either.                                         */
+#define NMGP_ERR_Y_ARG (-61)
+int64_t nmgp_y_workspace_size(int D, int N, int S);
+int nmgp_y_accum_f64(const double* pair_mu, const double* pair_sd, int64_t ld_pair, const double* G,
+                     const double* z_p, const double* z_f, int64_t z_stride, const int64_t* I, const double* y,
+                     double sd_err, int D, int N, int S, double* Y, double* F, double* F_sum, double* F_sq,
+                     double* L_sum, double* L_sq, double* G_sum, double* G_sq, double* lse_max, double* lse_sum,
+                     void* ws, int64_t ws_bytes, hipStream_t stream);
+
 /* Whole-step HIP graphs (the reference runs its step eagerly, code/nmgp_dsvi.py:829-854; the build captures
  * noise -> forward -> backward -> Adam once and replays it).  Capture goes straight through the HIP runtime:
  * begin on `stream` (thread-local mode; other streams join through event waits and must join back before
