@@ -228,6 +228,10 @@ _SIGS = {
     "nmgp_y_workspace_size": (c_i64, [c_int, c_int, c_int]),
     "nmgp_y_accum_f64": (c_int, [c_vp, c_vp, c_i64, c_vp, c_vp, c_vp, c_i64, c_vp, c_vp, c_dbl, c_int, c_int, c_int,
                                  c_vp, c_vp, c_vp, c_vp, c_vp, c_vp, c_vp, c_vp, c_vp, c_vp, c_vp, c_i64, c_vp]),
+    "nmgp_quantile_rows_max_S": (c_int, []),
+    "nmgp_corr_collect_f64": (c_int, [c_vp, c_vp, c_i64, c_vp, c_i64, c_vp, c_vp, c_int, c_int, c_int, c_int, c_vp,
+                                      c_i64, c_i64, c_vp]),
+    "nmgp_quantile_rows_f64": (c_int, [c_vp, c_i64, c_int, c_i64, c_vp, c_int, c_vp, c_vp]),
     "nmgp_counter_add": (c_int, [c_vp, c_i64, c_vp]),
     "nmgp_pbar_reduce_f64": (c_int, [c_vp, c_i64, c_vp, c_i64, c_vp, c_int, c_int, c_int, c_vp]),
     "nmgp_pbar_reduce_f32": (c_int, [c_vp, c_i64, c_vp, c_i64, c_vp, c_int, c_int, c_int, c_vp]),

@@ -1155,6 +1155,58 @@ def fy_accum_(pair_mu, pair_sd, G, z_p, z_f, sd_err, Y, corr_sum, corr_sq, ws=No
                                   L.ptr(ws) if need > 0 else None, need, L.stream_handle()), "fy_accum")
 
 
+def corr_collect_(pair_mu, pair_sd, z_p, pi, pj, C, s_off=0):
+    """One chunk of per-sample correlations of the listed output pairs (csrc/corrq.hip): C[p, n, s_off + s] is
+    written for the S samples of z_p; nothing is accumulated.  pair_mu / pair_sd (Q, N) may have a row stride;
+    z_p (S, >= Q N) is a column range of a noise block (unit column stride); pi / pj (P) int32 device vectors;
+    C (P, N, ld_c) contiguous with ld_c >= s_off + S."""
+    for name, t in (("pair_mu", pair_mu), ("pair_sd", pair_sd), ("z_p", z_p), ("C", C)):
+        L.require_device(t, name)
+        assert t.dtype == torch.float64, name
+    for name, t in (("pi", pi), ("pj", pj)):
+        L.require_device(t, name)
+        assert t.dtype == torch.int32 and t.dim() == 1 and t.is_contiguous(), name
+    Q, N = pair_mu.shape
+    D = int(((8 * Q + 1) ** 0.5 - 1) / 2 + 0.5)
+    assert D * (D + 1) // 2 == Q and pair_sd.shape == (Q, N)
+    assert pair_mu.stride(1) == 1 and pair_sd.stride(1) == 1 and pair_mu.stride(0) == pair_sd.stride(0) >= N
+    P = pi.numel()
+    assert pj.numel() == P
+    assert C.dim() == 3 and C.shape[:2] == (P, N) and C.is_contiguous()
+    assert z_p.dim() == 2 and z_p.shape[1] >= Q * N and (z_p.stride(1) == 1 or z_p.shape[1] == 1)
+    S = z_p.shape[0]
+    s_off = int(s_off)
+    assert 0 <= s_off and s_off + S <= C.shape[2]
+    z_stride = z_p.stride(0) if S > 1 else 0
+    L.check(L.lib().nmgp_corr_collect_f64(L.ptr(pair_mu), L.ptr(pair_sd), pair_mu.stride(0), L.ptr(z_p), int(z_stride),
+                                          L.ptr(pi), L.ptr(pj), P, D, N, S, L.ptr(C), C.shape[2], s_off,
+                                          L.stream_handle()), "corr_collect")
+    return C
+
+
+def quantile_rows_max_S():
+    """The longest row quantile_rows sorts (one workgroup's LDS)."""
+    return int(L.lib().nmgp_quantile_rows_max_S())
+
+
+def quantile_rows(C, qs):
+    """Exact quantiles (np.quantile's linear method) of every row of the (rows, S) device matrix C, by a sort inside
+    LDS (csrc/corrq.hip) -> (len(qs), rows).  C may be a column range of a wider matrix (row stride >= S, unit
+    column stride) and is not modified; a row with a NaN gives NaN.  S <= quantile_rows_max_S()."""
+    L.require_device(C, "C")
+    assert C.dtype == torch.float64 and C.dim() == 2
+    rows, S = C.shape
+    assert C.stride(1) == 1 or S == 1
+    ld = C.stride(0) if rows > 1 else S
+    assert ld >= S
+    qs = [float(q) for q in qs]
+    out = torch.empty(len(qs), rows, dtype=torch.float64, device=C.device)
+    arr = (ctypes.c_double * max(1, len(qs)))(*qs)
+    L.check(L.lib().nmgp_quantile_rows_f64(L.ptr(C), rows, S, ld, ctypes.cast(arr, ctypes.c_void_p), len(qs),
+                                           L.ptr(out), L.stream_handle()), "quantile_rows")
+    return out
+
+
 def y_workspace(D, N, S, device):
     """Workspace of y_accum_ for chunks of up to S samples (the sample slices' partial sums), or None when the
     samples are not sliced.  The size does not decrease with S, so a shorter last chunk fits."""

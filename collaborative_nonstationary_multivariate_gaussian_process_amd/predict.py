@@ -157,6 +157,11 @@ class _Draws:
         self.pos += n
         return out.reshape(S, per_sample)
 
+    def rewind(self):
+        """Back to the first sample: the same takes give the same noise again (the tape, or Philox, which is a
+        pure function of (seed, position))."""
+        self.pos = 0
+
 
 def _tril(t):
     return torch.tril(t)
@@ -351,19 +356,71 @@ def _quantiles_dim0(t, qs):
     return torch.stack(out)
 
 
-def summarize_FY(model, x, n_sample=1000, quantiles=(0.025, 0.975), noise_tape=None, keep_samples=False):
+def _parse_corr_pairs(corr_pairs, D):
+    """corr_pairs of summarize_FY -> (P, 2) int64 CPU tensor: "all" is every (i, j < i) in row order, else a
+    sequence of (i, j) with 0 <= i, j < D, order and duplicates kept."""
+    if isinstance(corr_pairs, str):
+        if corr_pairs != "all":
+            raise ValueError('corr_pairs: the only string accepted is "all"')
+        lst = [(i, j) for i in range(D) for j in range(i)]
+    else:
+        try:
+            lst = [tuple(int(v) for v in p) for p in corr_pairs]
+        except (TypeError, ValueError):
+            raise ValueError('corr_pairs must be None, "all" or a sequence of (i, j) pairs') from None
+        if any(len(p) != 2 for p in lst):
+            raise ValueError("corr_pairs: every entry must be an (i, j) pair")
+        if any(not (0 <= i < D and 0 <= j < D) for i, j in lst):
+            raise ValueError(f"corr_pairs: output indices must lie in 0..{D - 1}")
+    return torch.tensor(lst, dtype=torch.long).reshape(len(lst), 2)
+
+
+def _band_quantiles(C, qs):
+    """Quantiles along the last axis of the collected correlations C (pairs, N, S) -> (len(qs), N, pairs): the
+    LDS sort of csrc/corrq.hip, or, for more samples than one workgroup sorts, torch.sort and the same
+    interpolation (a row with a NaN is NaN, as np.quantile has it)."""
+    pb, N, S = C.shape
+    if S <= H.quantile_rows_max_S():
+        out = H.quantile_rows(C.reshape(pb * N, S), qs)
+    else:
+        srt = torch.sort(C.reshape(pb * N, S), dim=1).values
+        bad = torch.isnan(srt[:, -1])
+        rows = []
+        for q in qs:
+            pos = q * (S - 1)
+            lo = min(max(int(np.floor(pos)), 0), S - 1)
+            hi = min(lo + 1, S - 1)
+            r = srt[:, lo] if pos == lo else torch.lerp(srt[:, lo], srt[:, hi], pos - lo)
+            rows.append(torch.where(bad, torch.full_like(r, float("nan")), r))
+        out = torch.stack(rows)
+    return out.reshape(len(qs), pb, N).permute(0, 2, 1)
+
+
+def summarize_FY(model, x, n_sample=1000, quantiles=(0.025, 0.975), noise_tape=None, keep_samples=False,
+                 corr_pairs=None, band_bytes=1 << 30):
     """What the reference's drivers keep of NMGP.sample_FY (code/nmgp_dsvi.py:492-580; NMGP_ECoG_full.py:329-332):
     means and quantile bands of tilde_ell and Y, mean and population sd of the output correlations, as a dict of
     device tensors.  Same setup, chunking, noise layout and stream as sample_FY; each chunk's tail (pair samples,
     L, Y, L L^T, normalisation, accumulation over the samples) is one fused launch (csrc/fy.hip), so only
     O(S N D + N D^2) is ever stored -- the (S, N, D, D) correlation samples are not.  keep_samples=True adds
-    Ys (S, N, D) and tilde_ells (S, N)."""
+    Ys (S, N, D) and tilde_ells (S, N).
+
+    corr_pairs ("all" = every (i, j < i) in row order, or a sequence of (i, j)) adds the credible bands the
+    reference plots (code/utils.py:354-366, plot_corrs): "corr_pairs" (P, 2) int64 and "corr_quantiles"
+    (len(quantiles), N, P), whose [:, :, p] is np.quantile(corrs[:, :, i, j], quantiles, axis=0) of the very
+    samples whose mean is corr_mean.  The pairs are taken in batches of max(1, band_bytes // (8 S N)): a batch's
+    samples (pairs, N, S) are collected chunk by chunk (csrc/corrq.hip) and sorted inside LDS.  The first batch
+    rides along with the summary's chunks; every further batch walks the same noise stream again (the tape, or
+    Philox from position 0 with the same seed) and runs neither the sampling head nor fy.hip.  The result does not
+    depend on band_bytes.  With n_sample above hip_ops.quantile_rows_max_S() (16384) the collected batch is sorted
+    by torch.sort instead, with the same interpolation; that sort holds a second copy of the batch."""
     qs = [float(q) for q in quantiles]
     if any(not 0.0 <= q <= 1.0 for q in qs):
         raise ValueError("quantiles must lie in [0, 1]")
     n_sample = int(n_sample)
     if n_sample < 1:
         raise ValueError("n_sample must be at least 1")
+    pairs_t = None if corr_pairs is None else _parse_corr_pairs(corr_pairs, model.D)
     dev = model.device_
     x = torch.as_tensor(x).reshape(-1, 1).to(F64).to(dev).contiguous()
     st = _sampling_setup(model, x)
@@ -380,6 +437,13 @@ def summarize_FY(model, x, n_sample=1000, quantiles=(0.025, 0.975), noise_tape=N
     csq = torch.zeros(N, D, D, dtype=F64, device=dev)
     chunk = _chunk_size(n_sample, N, M)
     ws = H.fy_workspace(D, N, chunk, dev)
+    P = 0 if pairs_t is None else pairs_t.shape[0]
+    if P:
+        pb = min(P, max(1, int(band_bytes) // (8 * n_sample * N)))       # pairs per batch
+        pij = pairs_t.to(torch.int32).to(dev)
+        pi, pj = pij[:, 0].contiguous(), pij[:, 1].contiguous()
+        Cb = torch.empty(pb, N, n_sample, dtype=F64, device=dev)
+        cq = torch.empty(len(qs), N, P, dtype=F64, device=dev)
     done = 0
     while done < n_sample:
         S = min(chunk, n_sample - done)
@@ -388,6 +452,8 @@ def summarize_FY(model, x, n_sample=1000, quantiles=(0.025, 0.975), noise_tape=N
         Ts[done:done + S] = T
         H.fy_accum_(st["pair_mu"], st["pair_sd"], G.contiguous(), zc[:, o_p:], zc[:, o_f:], sd_err,
                     Ys[done:done + S], csum, csq, ws=ws)
+        if P:
+            H.corr_collect_(st["pair_mu"], st["pair_sd"], zc[:, o_p:], pi[:pb], pj[:pb], Cb, s_off=done)
         done += S
     mean = csum / n_sample
     out = {"tilde_ell_mean": Ts.mean(0), "tilde_ell_quantiles": _quantiles_dim0(Ts, qs),
@@ -395,6 +461,26 @@ def summarize_FY(model, x, n_sample=1000, quantiles=(0.025, 0.975), noise_tape=N
            "corr_mean": mean, "corr_sd": torch.sqrt(torch.clamp(csq / n_sample - mean * mean, min=0.0))}
     if keep_samples:
         out["Ys"], out["tilde_ells"] = Ys, Ts
+    if pairs_t is not None:
+        if P:
+            del G, T, zc
+            o_p = M + N                                                   # the noise layout of _sample_TG
+            cq[:, :, :pb] = _band_quantiles(Cb, qs)
+            for p0 in range(pb, P, pb):
+                p1 = min(P, p0 + pb)
+                draws.rewind()
+                done = 0
+                while done < n_sample:
+                    S = min(chunk, n_sample - done)
+                    zc = draws.take(S, per)
+                    H.corr_collect_(st["pair_mu"], st["pair_sd"], zc[:, o_p:], pi[p0:p1], pj[p0:p1], Cb[:p1 - p0],
+                                    s_off=done)
+                    done += S
+                    del zc
+                cq[:, :, p0:p1] = _band_quantiles(Cb[:p1 - p0], qs)
+        else:
+            cq = torch.empty(len(qs), N, 0, dtype=F64, device=dev)
+        out["corr_pairs"], out["corr_quantiles"] = pairs_t.to(dev), cq
     return out
 
 

@@ -685,6 +685,44 @@ int nmgp_y_accum_f64(const double* pair_mu, const double* pair_sd, int64_t ld_pa
                      double* L_sum, double* L_sq, double* G_sum, double* G_sq, double* lse_max, double* lse_sum,
                      void* ws, int64_t ws_bytes, hipStream_t stream);
 
+/* Credible bands of the output correlations (code/utils.py:354-366, plot_corrs: np.quantile(sampled_corrs[:, :, i, j],
+ * (0.025, 0.975), axis=0) of NMGP.sample_FY's samples) without the (S, N, D, D) tensor.  fp64, two steps.
+ *
+ * nmgp_corr_collect_f64: per-sample correlations of a list of P output pairs (i, j) = (pi[p], pj[p]) (device int32
+ * arrays).  For every p < P, input n < N and sample s < S of this chunk, with q = a (a + 1) / 2 + b:
+ *   l_q = pair_mu[q * ld_pair + n] + pair_sd[q * ld_pair + n] * z_p[s * z_stride + q * N + n],
+ *   L_aa = exp(l), L_ab = l (b < a);  cov_ab = sum_{k <= min(a, b)} L_ak L_bk;
+ *   C[(p * N + n) * ld_c + s_off + s] = cov_ij * sqrt(1 / cov_ii) * sqrt(1 / cov_jj)   (code/nmgp_dsvi.py:567-569)
+ * -- the definitions and the normalisation order of nmgp_fy_accum_f64, so C holds the very samples whose mean is
+ * corr_mean.  i < j is allowed and gives the same bits as (j, i); a duplicate pair gives the same bits again;
+ * i == j gives exactly 1 where the expression is finite and NaN where it is not (cov_ii 0, inf or NaN).  L is zero
+ * above its diagonal and the reference multiplies the full matrices, so a non-finite cov_ii or cov_jj makes the
+ * pair NaN at that (n, s) (inf * 0), and only there.  pi / pj outside 0..D-1 cannot be validated on the host: that
+ * pair's P-slice of C is NaN, the other pairs are not affected.  C is WRITTEN, never accumulated, every element
+ * once: calls over disjoint sample ranges (s_off) give the same bits as one call.  The layout of C -- samples
+ * innermost, rows (p, n) -- is what nmgp_quantile_rows_f64 reads: rows = P * N, ld = ld_c.  All indexing is 64-bit.
+ *
+ * nmgp_quantile_rows_f64: exact order-statistic quantiles of `rows` rows of S values, row r at C + r * ld; elements
+ * past S are not read and C is not modified.  qs is a HOST array of nq quantiles in [0, 1] (passed to the kernel by
+ * value).  Each row is sorted inside LDS (bitonic network on S padded with +inf); with pos = q (S - 1),
+ * lo = floor(pos), a = x_(lo), b = x_(min(lo + 1, S - 1)), w = pos - lo:
+ *   out[k * rows + r] = a when w == 0, a + (b - a) w when w < 0.5, else b - (b - a) (1 - w)
+ * (torch.lerp; np.quantile's linear method).  A row with a NaN gives NaN for every quantile; +-inf sort as values.
+ * Rows of up to 128 values get a wave each, longer rows 128 or 256 threads; one workgroup sorts at most
+ * nmgp_quantile_rows_max_S() = 16384 values (128 KiB of the 160 KiB of LDS), a larger S is refused.  No atomics: the
+ * same call gives the same bits.
+ *
+ * Both return 0 and launch nothing when a count is 0, and NMGP_ERR_CORRQ_ARG before any launch when D is outside
+ * 1..128, a count or s_off is negative, a pointer is NULL, ld_pair < N, z_stride < 0, ld_c < s_off + S, ld < S,
+ * S > nmgp_quantile_rows_max_S(), or a quantile is outside [0, 1] (NaN included).                                 */
+#define NMGP_ERR_CORRQ_ARG (-62)
+int nmgp_quantile_rows_max_S(void);
+int nmgp_corr_collect_f64(const double* pair_mu, const double* pair_sd, int64_t ld_pair, const double* z_p,
+                          int64_t z_stride, const int32_t* pi, const int32_t* pj, int P, int D, int N, int S,
+                          double* C, int64_t ld_c, int64_t s_off, hipStream_t stream);
+int nmgp_quantile_rows_f64(const double* C, int64_t rows, int S, int64_t ld, const double* qs, int nq, double* out,
+                           hipStream_t stream);
+
 /* Whole-step HIP graphs (the reference runs its step eagerly, code/nmgp_dsvi.py:829-854; the build captures
  * noise -> forward -> backward -> Adam once and replays it).  Capture goes straight through the HIP runtime:
  * begin on `stream` (thread-local mode; other streams join through event waits and must join back before
