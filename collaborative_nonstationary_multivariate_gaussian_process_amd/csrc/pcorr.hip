@@ -1,0 +1,338 @@
+// Partial correlations of the outputs, fused like the correlations of fy.hip: per sample s and input n the pair
+// samples -> L, W = L^-1, Omega = W^T W = (L L^T)^-1, pcorr = -D^-1/2 Omega D^-1/2 (diagonal 1), accumulated over the
+// samples on the device and, for a list of pairs, collected per sample into the layout nmgp_quantile_rows_f64 sorts.
+// The (S, N, D, D) tensor is never stored.  The reference has no partial-correlation code; the quantity is a pure
+// function of the covariance of NMGP.sample_FY (reference code/nmgp_dsvi.py:567-569).
+//
+// One workgroup (4 waves) per (input n, slice of samples), L and W side by side in LDS in the tile layout of fy.hip
+// (fy_tiles.hpp; 2 x 72 KiB at D = 128, 2 x 20 KiB at D = 50, plus 1 KiB: under the CU's 160 KiB at every D <= 128).
+// The rows of L past D carry a unit diagonal, so W is [[W_D, 0], [0, I]] and Omega's leading block is untouched.
+//
+// The inverse: the 16 x 16 diagonal tiles are inverted by forward substitution, one tile per 16 lanes (lane = column
+// of the inverse, 120 chained fma), all NT <= 8 of them at once on the 16 lane groups of the workgroup.  The tiles
+// below go tile row by tile row, W(ti, tj) = -W(ti, ti) sum_{tj <= k < ti} L(ti, k) W(k, tj), on
+// v_mfma_f64_16x16x4_f64; the sum's accumulator registers are fed straight back as the B operand of the product
+// with W(ti, ti) (register r of the C layout holds k = (lane >> 4) + 4 r; the A operand is read in that k order),
+// so no LDS round trip lies between the two.  The ti tiles of a row are dealt to the 4 waves; a barrier ends each
+// row.  That recurrence is the serial part: row ti costs its longest wave ceil(ti / 4) chains of up to 4 ti + 4
+// dependent MFMAs, 176 MFMAs on the critical path at NT = 8 against 448 / 4 = 112 if the rows could overlap, and
+// NT barriers.  Splitting a tile's k sum over waves would shorten the chains but needs an LDS reduction and a
+// barrier per row more; the row-wise split is kept because Omega (480 MFMAs at NT = 8, no dependences between
+// tiles) is the larger half and runs perfectly dealt.  Omega tile (ti, tj <= ti) = sum_{kt >= ti} W(kt, ti)^T
+// W(kt, tj): both operands are read as 4 whole rows of a tile (512 contiguous bytes, no bank conflict), the tiles
+// are dealt round-robin and each wave keeps its tiles' running sums in registers across the slice's samples, as
+// fy.hip does.  The sums leave the workgroup once: onto pc_sum / pc_sq when the samples are not sliced, else into
+// the per-slice workspace that a second kernel adds up in slice order (no floating-point atomics).
+//
+// Pair collection: the normalised lower triangle is written over L (no longer needed), and thread t stores the
+// pairs t, t + 256, ... of the list to C[p, n, s_off + s].  The stores run along the pair axis, 8 bytes each, one
+// sample at a time: samples are NOT staged to make runs along s (that would take a third matrix in LDS at D = 128);
+// tools/pcorr_probe.py records what this plain form costs.
+#include "fy_tiles.hpp"
+
+namespace nmgp {
+
+template <int NT>
+__global__ __launch_bounds__(kFyThreads) void pcorr_accum_kernel(
+    const double* __restrict__ pair_mu, const double* __restrict__ pair_sd, int64_t ld_pair,
+    const double* __restrict__ z_p, int64_t z_stride, int D, int N, int S, int per, double* __restrict__ pc_sum,
+    double* __restrict__ pc_sq, const int32_t* __restrict__ pi, const int32_t* __restrict__ pj, int P,
+    double* __restrict__ C, int64_t ld_c, int64_t s_off, double* __restrict__ ws, int n_blocks) {
+  constexpr int T = NT * (NT + 1) / 2;                  // lower-triangular tiles
+  constexpr int KMAX = (T + kFyWaves - 1) / kFyWaves;   // Omega tiles of one wave
+  extern __shared__ __attribute__((aligned(16))) double pc_smem[];
+  double* Lt = pc_smem;                                 // T tiles: L, later the normalised result
+  double* Wt = Lt + T * kFyTileElems;                   // T tiles: L^-1
+  double* Is = Wt + T * kFyTileElems;                   // NT * 16: sqrt(1 / Omega_ii), 0 past D
+  __shared__ int bad_flag[2];                           // a diagonal of L that is 0, inf or NaN, by sample parity
+
+  const int bid = blockIdx.x;
+  const int n = (bid % kFyXcds) * (n_blocks / kFyXcds) + bid / kFyXcds;   // as fy.hip: neighbours share an XCD
+  if (n >= N) return;
+  const int slice = blockIdx.y;
+  const int s0 = slice * per, s1 = min(S, s0 + per);
+  const int tid = threadIdx.x, lane = tid & 63, wave = uniform32(tid >> 6);
+  const int Q = D * (D + 1) / 2;
+  const bool accumulate = pc_sum != nullptr;
+
+  for (int e = tid; e < 2 * T * kFyTileElems + NT * kFyTile; e += kFyThreads) pc_smem[e] = 0.0;
+  if (tid < 2) bad_flag[tid] = 0;
+  __syncthreads();
+  // unit diagonal in the rows past D (never overwritten: the pair samples and the results stay inside D)
+  if (tid >= D && tid < NT * kFyTile)
+    Lt[(fy_ntiles(tid >> 4) + (tid >> 4)) * kFyTileElems + fy_tile_off(tid & 15, tid & 15)] = 1.0;
+
+  f64x4 sum[KMAX], sq[KMAX];
+#pragma unroll
+  for (int k = 0; k < KMAX; ++k) sum[k] = sq[k] = f64x4{0.0, 0.0, 0.0, 0.0};
+
+  const int ar = lane & 15, ak = lane >> 4;             // MFMA operand row / k of this lane
+  const double nan = __builtin_nan("");
+  __syncthreads();
+
+  for (int s = s0; s < s1; ++s) {
+    // ---- pair samples -> L tiles
+    const double* zp = z_p + (int64_t)s * z_stride + n;
+#pragma unroll 1
+    for (int q = tid; q < Q; q += kFyThreads) {
+      const int i = fy_tri_row(q);
+      const int j = q - i * (i + 1) / 2;
+      double l = pair_mu[(int64_t)q * ld_pair + n] + pair_sd[(int64_t)q * ld_pair + n] * zp[(int64_t)q * N];
+      if (i == j) {
+        l = exp(l);
+        if (!(__builtin_isfinite(l) && l != 0.0)) bad_flag[s & 1] = 1;
+      }
+      Lt[(fy_ntiles(i >> 4) + (j >> 4)) * kFyTileElems + fy_tile_off(i & 15, j & 15)] = l;
+    }
+    if (tid == 0) bad_flag[(s + 1) & 1] = 0;            // last read two barriers before the end of sample s - 1
+    __syncthreads();
+    const bool bad = bad_flag[s & 1] != 0;
+
+    // ---- diagonal tiles of W by forward substitution: tile t on wave t & 3, lanes 16 (t >> 2) ... + 15, lane =
+    // column c of the inverse.  Lane groups without a tile redo the last one and store nothing.
+    {
+      const int t = ak * kFyWaves + wave, tc = min(t, NT - 1);
+      const double* Ld = Lt + (fy_ntiles(tc) + tc) * kFyTileElems;
+      const double dinv = 1.0 / Ld[fy_tile_off(ar, ar)];
+      double x[kFyTile];
+#pragma unroll
+      for (int i = 0; i < kFyTile; ++i) {
+        double a = i == ar ? 1.0 : 0.0;
+#pragma unroll
+        for (int k = 0; k < i; ++k) a = fma(-Ld[fy_tile_off(i, k)], x[k], a);
+        x[i] = a * __shfl(dinv, (lane & 48) + i, 64);
+      }
+      if (t < NT) {
+        double* Wd = Wt + (fy_ntiles(t) + t) * kFyTileElems;
+#pragma unroll
+        for (int i = 0; i < kFyTile; ++i) Wd[fy_tile_off(i, ar)] = x[i];
+      }
+    }
+    __syncthreads();
+
+    // ---- the tiles below the diagonal, tile row by tile row
+    for (int ti = 1; ti < NT; ++ti) {
+      const double* Dt = Wt + (fy_ntiles(ti) + ti) * kFyTileElems;
+      for (int tj = wave; tj < ti; tj += kFyWaves) {
+        f64x4 acc = {0.0, 0.0, 0.0, 0.0};
+        for (int k = tj; k < ti; ++k) {
+          const double* At = Lt + (fy_ntiles(ti) + k) * kFyTileElems;
+          const double* Bt = Wt + (fy_ntiles(k) + tj) * kFyTileElems;
+#pragma unroll
+          for (int kk = 0; kk < 4; ++kk)
+            acc = Mfma<double>::mma(At[fy_tile_off(ar, kk * 4 + ak)], Bt[fy_tile_off(kk * 4 + ak, ar)], acc);
+        }
+        f64x4 w = {0.0, 0.0, 0.0, 0.0};
+#pragma unroll
+        for (int r = 0; r < 4; ++r) w = Mfma<double>::mma(Dt[fy_tile_off(ar, Mfma<double>::row(lane, r))], acc[r], w);
+        double* Wo = Wt + (fy_ntiles(ti) + tj) * kFyTileElems;
+#pragma unroll
+        for (int r = 0; r < 4; ++r) Wo[fy_tile_off(Mfma<double>::row(lane, r), ar)] = -w[r];
+      }
+      __syncthreads();
+    }
+
+    // ---- the diagonal of Omega: two threads per column of W, rows of one parity each
+    {
+      const int col = tid >> 1, half = tid & 1;
+      double c = 0.0;
+      if (col < D) {
+        const int tj = col >> 4, cc = col & 15;
+        for (int k = tj * kFyTile + half; k < NT * kFyTile; k += 2) {
+          const double v = Wt[(fy_ntiles(k >> 4) + tj) * kFyTileElems + fy_tile_off(k & 15, cc)];
+          c = fma(v, v, c);
+        }
+      }
+      c += __shfl_xor(c, 1, 64);
+      if (col < D && half == 0) Is[col] = sqrt(1.0 / c);
+    }
+    __syncthreads();
+
+    // ---- Omega tiles on the matrix cores, normalised, accumulated and (for the pair list) left in LDS over L
+    int tw = wave;
+    asm volatile("" : "+s"(tw));                        // tile coordinates recomputed per sample, as fy.hip
+#pragma unroll
+    for (int k = 0; k < KMAX; ++k) {
+      const int t = tw + k * kFyWaves;
+      if (t < T) {
+        const int ti = uniform32(fy_tri_row(t));
+        const int tj = t - fy_ntiles(ti);
+        f64x4 acc = {0.0, 0.0, 0.0, 0.0};
+        for (int kt = ti; kt < NT; ++kt) {
+          const double* At = Wt + (fy_ntiles(kt) + ti) * kFyTileElems;
+          const double* Bt = Wt + (fy_ntiles(kt) + tj) * kFyTileElems;
+#pragma unroll
+          for (int kk = 0; kk < 4; ++kk) {
+            const int o = fy_tile_off(kk * 4 + ak, ar);
+            acc = Mfma<double>::mma(At[o], Bt[o], acc);
+          }
+        }
+        const double isj = Is[tj * kFyTile + ar];
+        double* Ro = Lt + (fy_ntiles(ti) + tj) * kFyTileElems;
+#pragma unroll
+        for (int r = 0; r < 4; ++r) {
+          const int row = Mfma<double>::row(lane, r);
+          const double isi = Is[ti * kFyTile + row];
+          // the diagonal is 1, not 1 +- rounding (E[c^2] - mean^2 must be 0 there); a sample with a non-finite
+          // or zero diagonal of L is NaN everywhere
+          double c = -acc[r] * isi * isj;
+          if (ti == tj && row == ar) c = 1.0;
+          if (bad) c = nan;
+          if (accumulate) {
+            sum[k][r] += c;
+            sq[k][r] = fma(c, c, sq[k][r]);
+          }
+          // inside D and on or below the diagonal only: the zeros above it and the unit diagonal past D stay
+          if (P > 0 && ti * kFyTile + row < D && (ti > tj || ar <= row)) Ro[fy_tile_off(row, ar)] = c;
+        }
+      }
+    }
+    __syncthreads();
+
+    // ---- the listed pairs of this sample
+    if (P > 0) {
+      for (int p = tid; p < P; p += kFyThreads) {
+        const int i = pi[p], j = pj[p];
+        const int a = max(i, j), b = min(i, j);
+        double v = nan;
+        if (b >= 0 && a < D) v = Lt[(fy_ntiles(a >> 4) + (b >> 4)) * kFyTileElems + fy_tile_off(a & 15, b & 15)];
+        C[((int64_t)p * N + n) * ld_c + s_off + s] = v;
+      }
+      __syncthreads();
+    }
+  }
+
+  if (!accumulate) return;
+  // ---- the slice's sums leave the workgroup: lower triangle held, both triangles written
+  const int64_t dd = (int64_t)D * D;
+  const bool direct = gridDim.y == 1;
+  double* o_sum = direct ? pc_sum + (int64_t)n * dd : ws + (((int64_t)slice * N + n) * 2) * dd;
+  double* o_sq = direct ? pc_sq + (int64_t)n * dd : o_sum + dd;
+#pragma unroll
+  for (int k = 0; k < KMAX; ++k) {
+    const int t = wave + k * kFyWaves;
+    if (t < T) {
+      const int ti = uniform32(fy_tri_row(t));
+      const int tj = t - fy_ntiles(ti);
+      const int j = tj * kFyTile + ar;
+#pragma unroll
+      for (int r = 0; r < 4; ++r) {
+        const int i = ti * kFyTile + Mfma<double>::row(lane, r);
+        if (i < D && j <= i) {
+          const int64_t a = (int64_t)i * D + j, b = (int64_t)j * D + i;
+          if (direct) {
+            o_sum[a] += sum[k][r];
+            o_sq[a] += sq[k][r];
+            if (j < i) {
+              o_sum[b] += sum[k][r];
+              o_sq[b] += sq[k][r];
+            }
+          } else {
+            o_sum[a] = sum[k][r];
+            o_sq[a] = sq[k][r];
+          }
+        }
+      }
+    }
+  }
+}
+
+// pc_sum / pc_sq += the slices' partial sums, in slice order; one thread per (n, i, j), the partials hold the
+// lower triangle only.
+__global__ __launch_bounds__(256) void pcorr_reduce_kernel(const double* __restrict__ ws, int nsl, int D, int N,
+                                                            double* __restrict__ pc_sum, double* __restrict__ pc_sq) {
+  const int64_t dd = (int64_t)D * D;
+  const int64_t e = (int64_t)blockIdx.x * 256 + threadIdx.x;
+  if (e >= (int64_t)N * dd) return;
+  const int64_t n = e / dd;
+  const int ij = (int)(e - n * dd), i = ij / D, j = ij - i * D;
+  const int64_t src = (int64_t)max(i, j) * D + min(i, j);
+  double a = 0.0, b = 0.0;
+  for (int sl = 0; sl < nsl; ++sl) {
+    const double* p = ws + (((int64_t)sl * N + n) * 2) * dd + src;
+    a += p[0];
+    b += p[dd];
+  }
+  pc_sum[e] += a;
+  pc_sq[e] += b;
+}
+
+template <int NT>
+static int pcorr_launch(const double* pair_mu, const double* pair_sd, int64_t ld_pair, const double* z_p,
+                        int64_t z_stride, int D, int N, int S, int nsl, int per, double* pc_sum, double* pc_sq,
+                        const int32_t* pi, const int32_t* pj, int P, double* C, int64_t ld_c, int64_t s_off,
+                        double* ws, hipStream_t s) {
+  const size_t smem = (size_t)(2 * fy_ntiles(NT) * kFyTileElems + NT * kFyTile) * sizeof(double);
+  static bool attr_done = false;
+  if (!attr_done) {
+    (void)hipFuncSetAttribute((const void*)pcorr_accum_kernel<NT>, hipFuncAttributeMaxDynamicSharedMemorySize,
+                              (int)smem);
+    attr_done = true;
+  }
+  const int n_blocks = (N + kFyXcds - 1) / kFyXcds * kFyXcds;
+  hipLaunchKernelGGL(pcorr_accum_kernel<NT>, dim3((unsigned)n_blocks, (unsigned)nsl), dim3(kFyThreads), smem, s,
+                     pair_mu, pair_sd, ld_pair, z_p, z_stride, D, N, S, per, pc_sum, pc_sq, pi, pj, P, C, ld_c, s_off,
+                     ws, n_blocks);
+  NMGP_CHECK_LAUNCH();
+  return NMGP_OK;
+}
+
+}  // namespace nmgp
+
+using namespace nmgp;
+
+extern "C" {
+
+int64_t nmgp_pcorr_workspace_size(int D, int N, int S) {
+  if (D < 1 || D > kFyMaxD || N <= 0 || S <= 0) return 0;
+  int nsl, per;
+  fy_slicing(N, S, &nsl, &per);
+  return nsl == 1 ? 0 : (int64_t)nsl * N * 2 * D * D * (int64_t)sizeof(double);
+}
+
+int nmgp_pcorr_accum_f64(const double* pair_mu, const double* pair_sd, int64_t ld_pair, const double* z_p,
+                         int64_t z_stride, int D, int N, int S, double* pc_sum, double* pc_sq, const int32_t* pi,
+                         const int32_t* pj, int P, double* C, int64_t ld_c, int64_t s_off, void* ws, int64_t ws_bytes,
+                         hipStream_t stream) {
+  if (D < 1 || D > kFyMaxD || N < 0 || S < 0 || P < 0 || s_off < 0) return NMGP_ERR_PCORR_ARG;
+  if ((pc_sum == nullptr) != (pc_sq == nullptr)) return NMGP_ERR_PCORR_ARG;
+  if (!pc_sum && P == 0) return NMGP_ERR_PCORR_ARG;
+  if (N == 0 || S == 0) return NMGP_OK;
+  if (!pair_mu || !pair_sd || !z_p) return NMGP_ERR_PCORR_ARG;
+  if (ld_pair < N || z_stride < 0 || N > 0x7fffffff - kFyXcds) return NMGP_ERR_PCORR_ARG;
+  if (P > 0 && (!pi || !pj || !C || ld_c < s_off + S)) return NMGP_ERR_PCORR_ARG;
+  int nsl, per;
+  fy_slicing(N, S, &nsl, &per);
+  const int64_t need = pc_sum ? nmgp_pcorr_workspace_size(D, N, S) : 0;
+  if (need > 0 && (!ws || ws_bytes < need)) return NMGP_ERR_PCORR_ARG;
+  const int nt = (D + kFyTile - 1) / kFyTile;
+  int rc;
+#define NMGP_PCORR_CASE(NT_)                                                                                       \
+  case NT_:                                                                                                        \
+    rc = pcorr_launch<NT_>(pair_mu, pair_sd, ld_pair, z_p, z_stride, D, N, S, nsl, per, pc_sum, pc_sq, pi, pj, P, \
+                           C, ld_c, s_off, (double*)ws, stream);                                                   \
+    break;
+  switch (nt) {
+    NMGP_PCORR_CASE(1)
+    NMGP_PCORR_CASE(2)
+    NMGP_PCORR_CASE(3)
+    NMGP_PCORR_CASE(4)
+    NMGP_PCORR_CASE(5)
+    NMGP_PCORR_CASE(6)
+    NMGP_PCORR_CASE(7)
+    NMGP_PCORR_CASE(8)
+    default:
+      return NMGP_ERR_PCORR_ARG;
+  }
+#undef NMGP_PCORR_CASE
+  if (rc != NMGP_OK) return rc;
+  if (pc_sum && nsl > 1) {
+    const int64_t total = (int64_t)N * D * D;
+    hipLaunchKernelGGL(pcorr_reduce_kernel, dim3((unsigned)((total + 255) / 256)), dim3(256), 0, stream,
+                       (const double*)ws, nsl, D, N, pc_sum, pc_sq);
+    NMGP_CHECK_LAUNCH();
+  }
+  return NMGP_OK;
+}
+
+}  // extern "C"

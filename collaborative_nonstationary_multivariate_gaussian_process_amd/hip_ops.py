@@ -1184,6 +1184,61 @@ def corr_collect_(pair_mu, pair_sd, z_p, pi, pj, C, s_off=0):
     return C
 
 
+def pcorr_workspace(D, N, S, device):
+    """Workspace of pcorr_accum_ for chunks of up to S samples (the slices' partial sums), or None when the samples
+    are not sliced (N >= 256 or S == 1)."""
+    # as fy_workspace: a shorter last chunk can be cut into more slices than a full one
+    need = max(L.lib().nmgp_pcorr_workspace_size(D, N, s) for s in {S, min(S, max(1, 512 // max(N, 1)))})
+    return torch.empty(need, dtype=torch.uint8, device=device) if need > 0 else None
+
+
+def pcorr_accum_(pair_mu, pair_sd, z_p, pc_sum=None, pc_sq=None, pi=None, pj=None, C=None, s_off=0, ws=None):
+    """One chunk of the fused partial correlations (csrc/pcorr.hip): per sample and input L^-1, (L L^T)^-1 and its
+    normalisation.  pc_sum / pc_sq (N, D, D) are accumulated onto (both None: collect only); with a pair list
+    pi / pj (P) int32 device vectors, C[p, n, s_off + s] is written for the S samples of z_p.  pair_mu / pair_sd
+    (Q, N) may have a row stride; z_p (S, >= Q N) is a column range of a noise block (unit column stride); C
+    (P, N, ld_c) contiguous with ld_c >= s_off + S.  ws: pcorr_workspace(...) kept by a caller that runs several
+    chunks, else allocated here."""
+    for name, t in (("pair_mu", pair_mu), ("pair_sd", pair_sd), ("z_p", z_p)):
+        L.require_device(t, name)
+        assert t.dtype == torch.float64, name
+    Q, N = pair_mu.shape
+    D = int(((8 * Q + 1) ** 0.5 - 1) / 2 + 0.5)
+    assert D * (D + 1) // 2 == Q and pair_sd.shape == (Q, N)
+    assert pair_mu.stride(1) == 1 and pair_sd.stride(1) == 1 and pair_mu.stride(0) == pair_sd.stride(0) >= N
+    assert z_p.dim() == 2 and z_p.shape[1] >= Q * N and (z_p.stride(1) == 1 or z_p.shape[1] == 1)
+    S = z_p.shape[0]
+    z_stride = z_p.stride(0) if S > 1 else 0
+    assert (pc_sum is None) == (pc_sq is None), "pc_sum and pc_sq go together"
+    sums = pc_sum is not None
+    if sums:
+        for name, t in (("pc_sum", pc_sum), ("pc_sq", pc_sq)):
+            L.require_device(t, name)
+            assert t.dtype == torch.float64 and t.shape == (N, D, D) and t.is_contiguous(), name
+    assert (pi is None) == (pj is None) == (C is None), "pi, pj and C go together"
+    P, ld_c, s_off = 0, 0, int(s_off)
+    if pi is not None:
+        for name, t in (("pi", pi), ("pj", pj)):
+            L.require_device(t, name)
+            assert t.dtype == torch.int32 and t.dim() == 1 and t.is_contiguous(), name
+        P = pi.numel()
+        assert pj.numel() == P
+        L.require_device(C, "C")
+        assert C.dtype == torch.float64 and C.dim() == 3 and C.shape[:2] == (P, N) and C.is_contiguous()
+        ld_c = C.shape[2]
+        assert 0 <= s_off and s_off + S <= ld_c
+    assert sums or P > 0, "nothing to do: neither sums nor a pair list"
+    lib = L.lib()
+    need = lib.nmgp_pcorr_workspace_size(D, N, S) if sums else 0
+    if need > 0 and (ws is None or ws.numel() * ws.element_size() < need):
+        ws = torch.empty(need, dtype=torch.uint8, device=z_p.device)                    # slices' partial sums
+    L.check(lib.nmgp_pcorr_accum_f64(L.ptr(pair_mu), L.ptr(pair_sd), pair_mu.stride(0), L.ptr(z_p), int(z_stride),
+                                     D, N, S, L.ptr(pc_sum), L.ptr(pc_sq), L.ptr(pi) if P else None,
+                                     L.ptr(pj) if P else None, P, L.ptr(C) if P else None, ld_c, s_off,
+                                     L.ptr(ws) if need > 0 else None, need, L.stream_handle()), "pcorr_accum")
+    return C
+
+
 def quantile_rows_max_S():
     """The longest row quantile_rows sorts (one workgroup's LDS)."""
     return int(L.lib().nmgp_quantile_rows_max_S())

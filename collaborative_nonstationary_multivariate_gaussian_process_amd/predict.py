@@ -397,7 +397,7 @@ def _band_quantiles(C, qs):
 
 
 def summarize_FY(model, x, n_sample=1000, quantiles=(0.025, 0.975), noise_tape=None, keep_samples=False,
-                 corr_pairs=None, band_bytes=1 << 30):
+                 corr_pairs=None, band_bytes=1 << 30, partial=False):
     """What the reference's drivers keep of NMGP.sample_FY (code/nmgp_dsvi.py:492-580; NMGP_ECoG_full.py:329-332):
     means and quantile bands of tilde_ell and Y, mean and population sd of the output correlations, as a dict of
     device tensors.  Same setup, chunking, noise layout and stream as sample_FY; each chunk's tail (pair samples,
@@ -413,7 +413,18 @@ def summarize_FY(model, x, n_sample=1000, quantiles=(0.025, 0.975), noise_tape=N
     rides along with the summary's chunks; every further batch walks the same noise stream again (the tape, or
     Philox from position 0 with the same seed) and runs neither the sampling head nor fy.hip.  The result does not
     depend on band_bytes.  With n_sample above hip_ops.quantile_rows_max_S() (16384) the collected batch is sorted
-    by torch.sort instead, with the same interpolation; that sort holds a second copy of the batch."""
+    by torch.sort instead, with the same interpolation; that sort holds a second copy of the batch.
+
+    partial=True adds the partial correlations of the outputs -- the correlation of outputs i and j given all the
+    others, -Omega_ij / sqrt(Omega_ii Omega_jj) with Omega = (L L^T)^-1 the sample's precision matrix, diagonal 1 --
+    as "pcorr_mean" and "pcorr_sd" (N, D, D; population sd, as corr_sd): the mean of the samples' partial
+    correlations, not the partial correlation of corr_mean.  Each chunk is one more fused launch (csrc/pcorr.hip:
+    L^-1 and L^-T L^-1 per sample and input inside one workgroup's LDS), again without an (S, N, D, D) tensor.  With
+    corr_pairs it also adds "pcorr_quantiles" (len(quantiles), N, P) for the same pair list, collected by the same
+    kernel into a second (pairs, N, S) batch buffer of the size band_bytes allows and sorted like the correlation
+    bands; the further batches run that kernel in collect-only mode.  A sample whose L has a zero or non-finite
+    diagonal entry at an input (an exp that under- or overflowed) is NaN in every partial correlation at that input.
+    With partial=False nothing is launched or returned for it."""
     qs = [float(q) for q in quantiles]
     if any(not 0.0 <= q <= 1.0 for q in qs):
         raise ValueError("quantiles must lie in [0, 1]")
@@ -438,12 +449,19 @@ def summarize_FY(model, x, n_sample=1000, quantiles=(0.025, 0.975), noise_tape=N
     chunk = _chunk_size(n_sample, N, M)
     ws = H.fy_workspace(D, N, chunk, dev)
     P = 0 if pairs_t is None else pairs_t.shape[0]
+    if partial:
+        psum = torch.zeros(N, D, D, dtype=F64, device=dev)
+        psq = torch.zeros(N, D, D, dtype=F64, device=dev)
+        pws = H.pcorr_workspace(D, N, chunk, dev)
     if P:
         pb = min(P, max(1, int(band_bytes) // (8 * n_sample * N)))       # pairs per batch
         pij = pairs_t.to(torch.int32).to(dev)
         pi, pj = pij[:, 0].contiguous(), pij[:, 1].contiguous()
         Cb = torch.empty(pb, N, n_sample, dtype=F64, device=dev)
         cq = torch.empty(len(qs), N, P, dtype=F64, device=dev)
+        if partial:
+            Pb = torch.empty(pb, N, n_sample, dtype=F64, device=dev)
+            pq = torch.empty(len(qs), N, P, dtype=F64, device=dev)
     done = 0
     while done < n_sample:
         S = min(chunk, n_sample - done)
@@ -454,11 +472,20 @@ def summarize_FY(model, x, n_sample=1000, quantiles=(0.025, 0.975), noise_tape=N
                     Ys[done:done + S], csum, csq, ws=ws)
         if P:
             H.corr_collect_(st["pair_mu"], st["pair_sd"], zc[:, o_p:], pi[:pb], pj[:pb], Cb, s_off=done)
+        if partial and P:
+            H.pcorr_accum_(st["pair_mu"], st["pair_sd"], zc[:, o_p:], psum, psq, pi[:pb], pj[:pb], Pb, s_off=done,
+                           ws=pws)
+        elif partial:
+            H.pcorr_accum_(st["pair_mu"], st["pair_sd"], zc[:, o_p:], psum, psq, ws=pws)
         done += S
     mean = csum / n_sample
     out = {"tilde_ell_mean": Ts.mean(0), "tilde_ell_quantiles": _quantiles_dim0(Ts, qs),
            "Y_mean": Ys.mean(0), "Y_quantiles": _quantiles_dim0(Ys, qs),
            "corr_mean": mean, "corr_sd": torch.sqrt(torch.clamp(csq / n_sample - mean * mean, min=0.0))}
+    if partial:
+        pmean = psum / n_sample
+        out["pcorr_mean"] = pmean
+        out["pcorr_sd"] = torch.sqrt(torch.clamp(psq / n_sample - pmean * pmean, min=0.0))
     if keep_samples:
         out["Ys"], out["tilde_ells"] = Ys, Ts
     if pairs_t is not None:
@@ -466,6 +493,8 @@ def summarize_FY(model, x, n_sample=1000, quantiles=(0.025, 0.975), noise_tape=N
             del G, T, zc
             o_p = M + N                                                   # the noise layout of _sample_TG
             cq[:, :, :pb] = _band_quantiles(Cb, qs)
+            if partial:
+                pq[:, :, :pb] = _band_quantiles(Pb, qs)
             for p0 in range(pb, P, pb):
                 p1 = min(P, p0 + pb)
                 draws.rewind()
@@ -475,12 +504,20 @@ def summarize_FY(model, x, n_sample=1000, quantiles=(0.025, 0.975), noise_tape=N
                     zc = draws.take(S, per)
                     H.corr_collect_(st["pair_mu"], st["pair_sd"], zc[:, o_p:], pi[p0:p1], pj[p0:p1], Cb[:p1 - p0],
                                     s_off=done)
+                    if partial:
+                        H.pcorr_accum_(st["pair_mu"], st["pair_sd"], zc[:, o_p:], pi=pi[p0:p1], pj=pj[p0:p1],
+                                       C=Pb[:p1 - p0], s_off=done)
                     done += S
                     del zc
                 cq[:, :, p0:p1] = _band_quantiles(Cb[:p1 - p0], qs)
+                if partial:
+                    pq[:, :, p0:p1] = _band_quantiles(Pb[:p1 - p0], qs)
         else:
             cq = torch.empty(len(qs), N, 0, dtype=F64, device=dev)
+            pq = torch.empty(len(qs), N, 0, dtype=F64, device=dev)
         out["corr_pairs"], out["corr_quantiles"] = pairs_t.to(dev), cq
+        if partial:
+            out["pcorr_quantiles"] = pq
     return out
 
 

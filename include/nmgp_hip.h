@@ -723,6 +723,38 @@ int nmgp_corr_collect_f64(const double* pair_mu, const double* pair_sd, int64_t 
 int nmgp_quantile_rows_f64(const double* C, int64_t rows, int S, int64_t ld, const double* qs, int nq, double* out,
                            hipStream_t stream);
 
+/* Partial correlations of the outputs, the companion of the correlations of nmgp_fy_accum_f64: the correlation of
+ * outputs i and j given all the others, i.e. the normalised precision matrix.  The reference has no such code; the
+ * quantity is a function of NMGP.sample_FY's covariance L L^T (code/nmgp_dsvi.py:567-569) and is scale invariant.
+ * fp64.  For every sample s < S and input n < N, with L built from the pair samples exactly as in
+ * nmgp_fy_accum_f64 (l_q = pair_mu[q * ld_pair + n] + pair_sd[q * ld_pair + n] * z_p[s * z_stride + q * N + n],
+ * L_ii = exp(l), L_ij = l for j < i):
+ *   W = L^-1 (lower triangular: 16 x 16 diagonal tiles by substitution, the tiles below them tile row by tile row
+ *   on v_mfma_f64_16x16x4_f64),  Omega = W^T W = (L L^T)^-1 (lower triangle, matrix cores),
+ *   pcorr_ij = -Omega_ij * sqrt(1 / Omega_ii) * sqrt(1 / Omega_jj) for i != j,  pcorr_ii = 1 exactly;
+ *   if any L_kk of that sample at that input is 0, inf or NaN (an exp that under- or overflowed), EVERY pcorr_ij of
+ *   that sample at that input is NaN, the diagonal included; other inputs and samples are not affected;
+ *   pc_sum[(n * D + i) * D + j] += pcorr_ij, pc_sq[...] += pcorr_ij^2   (full symmetric D x D);
+ *   with a pair list (P > 0; pi / pj device int32): C[(p * N + n) * ld_c + s_off + s] = pcorr_{pi[p], pj[p]}.
+ * pc_sum / pc_sq ACCUMULATE (the caller zeroes them once; the chunks of one summary add up); both NULL = collect
+ * only: the same C bits are written and no sum (and no workspace) is touched.  C is WRITTEN, every element once, in
+ * the layout nmgp_quantile_rows_f64 reads (rows = P * N, ld = ld_c); (i, j) and (j, i) give the same bits, a
+ * duplicate pair the same bits again, i == j the diagonal value (1, or NaN by the rule above); pi / pj outside
+ * 0..D-1 cannot be validated on the host: that pair's slice of C is NaN.  The samples are cut into slices by the rule
+ * of nmgp_fy_accum_f64 (none when N >= 256); the slices' partial sums go through `ws` (nmgp_pcorr_workspace_size
+ * bytes, 0 when unsliced) and are added in slice order: no floating-point atomics, the same call gives the same
+ * bits.  L and W share one workgroup's LDS (2 x 72 KiB at D = 128).  All indexing is 64-bit.  Returns 0 (nothing
+ * launched when S == 0 or N == 0), NMGP_ERR_PCORR_ARG before any launch when D is outside 1..128, a count or s_off
+ * is negative, ld_pair < N, z_stride < 0, pair_mu / pair_sd / z_p is NULL, exactly one of pc_sum / pc_sq is NULL,
+ * the sums and the pair list are both absent, P > 0 and pi, pj or C is NULL or ld_c < s_off + S, or the sums are
+ * given and the workspace is missing / too small.                                                              */
+#define NMGP_ERR_PCORR_ARG (-63)
+int64_t nmgp_pcorr_workspace_size(int D, int N, int S);
+int nmgp_pcorr_accum_f64(const double* pair_mu, const double* pair_sd, int64_t ld_pair, const double* z_p,
+                         int64_t z_stride, int D, int N, int S, double* pc_sum, double* pc_sq, const int32_t* pi,
+                         const int32_t* pj, int P, double* C, int64_t ld_c, int64_t s_off, void* ws, int64_t ws_bytes,
+                         hipStream_t stream);
+
 /* Whole-step HIP graphs (the reference runs its step eagerly, code/nmgp_dsvi.py:829-854; the build captures
  * noise -> forward -> backward -> Adam once and replays it).  Capture goes straight through the HIP runtime:
  * begin on `stream` (thread-local mode; other streams join through event waits and must join back before
