@@ -28,7 +28,11 @@
 // pairs t, t + 256, ... of the list to C[p, n, s_off + s].  The stores run along the pair axis, 8 bytes each, one
 // sample at a time: samples are NOT staged to make runs along s (that would take a third matrix in LDS at D = 128);
 // tools/pcorr_probe.py records what this plain form costs.
-#include "fy_tiles.hpp"
+//
+// Group collection (nmgp_pcorr_accum_groups_f64): the same triangle over L, reduced per group of a table of (i, j)
+// groups by the device function that cgroup.hip uses (fy_groups.hpp) into Cg[k, n, sg_off + s].  Sums, pair list and
+// groups are three independent switches of the one launch; L^-1 and Omega are computed once for whichever are asked.
+#include "fy_groups.hpp"
 
 namespace nmgp {
 
@@ -37,7 +41,9 @@ __global__ __launch_bounds__(kFyThreads) void pcorr_accum_kernel(
     const double* __restrict__ pair_mu, const double* __restrict__ pair_sd, int64_t ld_pair,
     const double* __restrict__ z_p, int64_t z_stride, int D, int N, int S, int per, double* __restrict__ pc_sum,
     double* __restrict__ pc_sq, const int32_t* __restrict__ pi, const int32_t* __restrict__ pj, int P,
-    double* __restrict__ C, int64_t ld_c, int64_t s_off, double* __restrict__ ws, int n_blocks) {
+    double* __restrict__ C, int64_t ld_c, int64_t s_off, const int32_t* __restrict__ goff,
+    const uint32_t* __restrict__ gent, int K, int E, double* __restrict__ Cg, int64_t ld_cg, int64_t sg_off,
+    double* __restrict__ ws, int n_blocks) {
   constexpr int T = NT * (NT + 1) / 2;                  // lower-triangular tiles
   constexpr int KMAX = (T + kFyWaves - 1) / kFyWaves;   // Omega tiles of one wave
   extern __shared__ __attribute__((aligned(16))) double pc_smem[];
@@ -45,6 +51,7 @@ __global__ __launch_bounds__(kFyThreads) void pcorr_accum_kernel(
   double* Wt = Lt + T * kFyTileElems;                   // T tiles: L^-1
   double* Is = Wt + T * kFyTileElems;                   // NT * 16: sqrt(1 / Omega_ii), 0 past D
   __shared__ int bad_flag[2];                           // a diagonal of L that is 0, inf or NaN, by sample parity
+  __shared__ double part[2 * kFyWaves];                 // wave sums of a group that the whole workgroup adds
 
   const int bid = blockIdx.x;
   const int n = (bid % kFyXcds) * (n_blocks / kFyXcds) + bid / kFyXcds;   // as fy.hip: neighbours share an XCD
@@ -54,6 +61,8 @@ __global__ __launch_bounds__(kFyThreads) void pcorr_accum_kernel(
   const int tid = threadIdx.x, lane = tid & 63, wave = uniform32(tid >> 6);
   const int Q = D * (D + 1) / 2;
   const bool accumulate = pc_sum != nullptr;
+  const bool keep = P > 0 || K > 0;                     // the normalised triangle is wanted in LDS
+  int par = 0;
 
   for (int e = tid; e < 2 * T * kFyTileElems + NT * kFyTile; e += kFyThreads) pc_smem[e] = 0.0;
   if (tid < 2) bad_flag[tid] = 0;
@@ -183,14 +192,14 @@ __global__ __launch_bounds__(kFyThreads) void pcorr_accum_kernel(
             sq[k][r] = fma(c, c, sq[k][r]);
           }
           // inside D and on or below the diagonal only: the zeros above it and the unit diagonal past D stay
-          if (P > 0 && ti * kFyTile + row < D && (ti > tj || ar <= row)) Ro[fy_tile_off(row, ar)] = c;
+          if (keep && ti * kFyTile + row < D && (ti > tj || ar <= row)) Ro[fy_tile_off(row, ar)] = c;
         }
       }
     }
     __syncthreads();
 
-    // ---- the listed pairs of this sample
-    if (P > 0) {
+    // ---- the listed pairs and the groups of this sample
+    if (keep) {
       for (int p = tid; p < P; p += kFyThreads) {
         const int i = pi[p], j = pj[p];
         const int a = max(i, j), b = min(i, j);
@@ -198,6 +207,9 @@ __global__ __launch_bounds__(kFyThreads) void pcorr_accum_kernel(
         if (b >= 0 && a < D) v = Lt[(fy_ntiles(a >> 4) + (b >> 4)) * kFyTileElems + fy_tile_off(a & 15, b & 15)];
         C[((int64_t)p * N + n) * ld_c + s_off + s] = v;
       }
+      if (K > 0)
+        fy_group_reduce(Lt, D, goff, gent, K, E, part, par, Cg + (int64_t)n * ld_cg + sg_off + s,
+                        (int64_t)N * ld_cg, tid);
       __syncthreads();
     }
   }
@@ -261,7 +273,8 @@ template <int NT>
 static int pcorr_launch(const double* pair_mu, const double* pair_sd, int64_t ld_pair, const double* z_p,
                         int64_t z_stride, int D, int N, int S, int nsl, int per, double* pc_sum, double* pc_sq,
                         const int32_t* pi, const int32_t* pj, int P, double* C, int64_t ld_c, int64_t s_off,
-                        double* ws, hipStream_t s) {
+                        const int32_t* goff, const uint32_t* gent, int K, int E, double* Cg, int64_t ld_cg,
+                        int64_t sg_off, double* ws, hipStream_t s) {
   const size_t smem = (size_t)(2 * fy_ntiles(NT) * kFyTileElems + NT * kFyTile) * sizeof(double);
   static bool attr_done = false;
   if (!attr_done) {
@@ -272,7 +285,7 @@ static int pcorr_launch(const double* pair_mu, const double* pair_sd, int64_t ld
   const int n_blocks = (N + kFyXcds - 1) / kFyXcds * kFyXcds;
   hipLaunchKernelGGL(pcorr_accum_kernel<NT>, dim3((unsigned)n_blocks, (unsigned)nsl), dim3(kFyThreads), smem, s,
                      pair_mu, pair_sd, ld_pair, z_p, z_stride, D, N, S, per, pc_sum, pc_sq, pi, pj, P, C, ld_c, s_off,
-                     ws, n_blocks);
+                     goff, gent, K, E, Cg, ld_cg, sg_off, ws, n_blocks);
   NMGP_CHECK_LAUNCH();
   return NMGP_OK;
 }
@@ -290,17 +303,20 @@ int64_t nmgp_pcorr_workspace_size(int D, int N, int S) {
   return nsl == 1 ? 0 : (int64_t)nsl * N * 2 * D * D * (int64_t)sizeof(double);
 }
 
-int nmgp_pcorr_accum_f64(const double* pair_mu, const double* pair_sd, int64_t ld_pair, const double* z_p,
-                         int64_t z_stride, int D, int N, int S, double* pc_sum, double* pc_sq, const int32_t* pi,
-                         const int32_t* pj, int P, double* C, int64_t ld_c, int64_t s_off, void* ws, int64_t ws_bytes,
-                         hipStream_t stream) {
-  if (D < 1 || D > kFyMaxD || N < 0 || S < 0 || P < 0 || s_off < 0) return NMGP_ERR_PCORR_ARG;
+int nmgp_pcorr_accum_groups_f64(const double* pair_mu, const double* pair_sd, int64_t ld_pair, const double* z_p,
+                                int64_t z_stride, int D, int N, int S, double* pc_sum, double* pc_sq,
+                                const int32_t* pi, const int32_t* pj, int P, double* C, int64_t ld_c, int64_t s_off,
+                                const int32_t* goff, const int32_t* gent, int K, int E, double* Cg, int64_t ld_cg,
+                                int64_t sg_off, void* ws, int64_t ws_bytes, hipStream_t stream) {
+  if (D < 1 || D > kFyMaxD || N < 0 || S < 0 || P < 0 || s_off < 0 || K < 0 || sg_off < 0)
+    return NMGP_ERR_PCORR_ARG;
   if ((pc_sum == nullptr) != (pc_sq == nullptr)) return NMGP_ERR_PCORR_ARG;
-  if (!pc_sum && P == 0) return NMGP_ERR_PCORR_ARG;
+  if (!pc_sum && P == 0 && K == 0) return NMGP_ERR_PCORR_ARG;
   if (N == 0 || S == 0) return NMGP_OK;
   if (!pair_mu || !pair_sd || !z_p) return NMGP_ERR_PCORR_ARG;
   if (ld_pair < N || z_stride < 0 || N > 0x7fffffff - kFyXcds) return NMGP_ERR_PCORR_ARG;
   if (P > 0 && (!pi || !pj || !C || ld_c < s_off + S)) return NMGP_ERR_PCORR_ARG;
+  if (K > 0 && (!goff || !gent || !Cg || E < K || ld_cg < sg_off + S)) return NMGP_ERR_PCORR_ARG;
   int nsl, per;
   fy_slicing(N, S, &nsl, &per);
   const int64_t need = pc_sum ? nmgp_pcorr_workspace_size(D, N, S) : 0;
@@ -310,7 +326,8 @@ int nmgp_pcorr_accum_f64(const double* pair_mu, const double* pair_sd, int64_t l
 #define NMGP_PCORR_CASE(NT_)                                                                                       \
   case NT_:                                                                                                        \
     rc = pcorr_launch<NT_>(pair_mu, pair_sd, ld_pair, z_p, z_stride, D, N, S, nsl, per, pc_sum, pc_sq, pi, pj, P, \
-                           C, ld_c, s_off, (double*)ws, stream);                                                   \
+                           C, ld_c, s_off, goff, (const uint32_t*)gent, K, E, Cg, ld_cg, sg_off, (double*)ws,     \
+                           stream);                                                                                \
     break;
   switch (nt) {
     NMGP_PCORR_CASE(1)
@@ -333,6 +350,15 @@ int nmgp_pcorr_accum_f64(const double* pair_mu, const double* pair_sd, int64_t l
     NMGP_CHECK_LAUNCH();
   }
   return NMGP_OK;
+}
+
+// the form without groups: the same launch, K = 0
+int nmgp_pcorr_accum_f64(const double* pair_mu, const double* pair_sd, int64_t ld_pair, const double* z_p,
+                         int64_t z_stride, int D, int N, int S, double* pc_sum, double* pc_sq, const int32_t* pi,
+                         const int32_t* pj, int P, double* C, int64_t ld_c, int64_t s_off, void* ws, int64_t ws_bytes,
+                         hipStream_t stream) {
+  return nmgp_pcorr_accum_groups_f64(pair_mu, pair_sd, ld_pair, z_p, z_stride, D, N, S, pc_sum, pc_sq, pi, pj, P, C,
+                                     ld_c, s_off, nullptr, nullptr, 0, 0, nullptr, 0, 0, ws, ws_bytes, stream);
 }
 
 }  // extern "C"

@@ -1192,13 +1192,16 @@ def pcorr_workspace(D, N, S, device):
     return torch.empty(need, dtype=torch.uint8, device=device) if need > 0 else None
 
 
-def pcorr_accum_(pair_mu, pair_sd, z_p, pc_sum=None, pc_sq=None, pi=None, pj=None, C=None, s_off=0, ws=None):
+def pcorr_accum_(pair_mu, pair_sd, z_p, pc_sum=None, pc_sq=None, pi=None, pj=None, C=None, s_off=0, ws=None,
+                 goff=None, gent=None, Cg=None, sg_off=0):
     """One chunk of the fused partial correlations (csrc/pcorr.hip): per sample and input L^-1, (L L^T)^-1 and its
     normalisation.  pc_sum / pc_sq (N, D, D) are accumulated onto (both None: collect only); with a pair list
     pi / pj (P) int32 device vectors, C[p, n, s_off + s] is written for the S samples of z_p.  pair_mu / pair_sd
     (Q, N) may have a row stride; z_p (S, >= Q N) is a column range of a noise block (unit column stride); C
-    (P, N, ld_c) contiguous with ld_c >= s_off + S.  ws: pcorr_workspace(...) kept by a caller that runs several
-    chunks, else allocated here."""
+    (P, N, ld_c) contiguous with ld_c >= s_off + S.  With a group table (goff, gent) = group_table(...), the group
+    means of the sample's partial correlations are written to Cg[k, n, sg_off + s] (Cg (K, N, ld_cg) contiguous).
+    Sums, pair list and groups are independent of each other.  ws: pcorr_workspace(...) kept by a caller that runs
+    several chunks, else allocated here."""
     for name, t in (("pair_mu", pair_mu), ("pair_sd", pair_sd), ("z_p", z_p)):
         L.require_device(t, name)
         assert t.dtype == torch.float64, name
@@ -1227,15 +1230,85 @@ def pcorr_accum_(pair_mu, pair_sd, z_p, pc_sum=None, pc_sq=None, pi=None, pj=Non
         assert C.dtype == torch.float64 and C.dim() == 3 and C.shape[:2] == (P, N) and C.is_contiguous()
         ld_c = C.shape[2]
         assert 0 <= s_off and s_off + S <= ld_c
-    assert sums or P > 0, "nothing to do: neither sums nor a pair list"
+    assert (goff is None) == (gent is None) == (Cg is None), "goff, gent and Cg go together"
+    K, E, ld_cg, sg_off = 0, 0, 0, int(sg_off)
+    if goff is not None:
+        K, E = _check_group_args(goff, gent, Cg, N, S, sg_off, "Cg")
+        ld_cg = Cg.shape[2]
+    assert sums or P > 0 or K > 0, "nothing to do: neither sums nor a pair list nor groups"
     lib = L.lib()
     need = lib.nmgp_pcorr_workspace_size(D, N, S) if sums else 0
     if need > 0 and (ws is None or ws.numel() * ws.element_size() < need):
         ws = torch.empty(need, dtype=torch.uint8, device=z_p.device)                    # slices' partial sums
-    L.check(lib.nmgp_pcorr_accum_f64(L.ptr(pair_mu), L.ptr(pair_sd), pair_mu.stride(0), L.ptr(z_p), int(z_stride),
-                                     D, N, S, L.ptr(pc_sum), L.ptr(pc_sq), L.ptr(pi) if P else None,
-                                     L.ptr(pj) if P else None, P, L.ptr(C) if P else None, ld_c, s_off,
-                                     L.ptr(ws) if need > 0 else None, need, L.stream_handle()), "pcorr_accum")
+    head = (L.ptr(pair_mu), L.ptr(pair_sd), pair_mu.stride(0), L.ptr(z_p), int(z_stride), D, N, S, L.ptr(pc_sum),
+            L.ptr(pc_sq), L.ptr(pi) if P else None, L.ptr(pj) if P else None, P, L.ptr(C) if P else None, ld_c, s_off)
+    tail = (L.ptr(ws) if need > 0 else None, need, L.stream_handle())
+    if K:
+        L.check(lib.nmgp_pcorr_accum_groups_f64(*head, L.ptr(goff), L.ptr(gent), K, E, L.ptr(Cg), ld_cg, sg_off,
+                                                *tail), "pcorr_accum_groups")
+    else:
+        L.check(lib.nmgp_pcorr_accum_f64(*head, *tail), "pcorr_accum")
+    return C
+
+
+def group_table(groups, D, device):
+    """The CSR table of corr_group_ / pcorr_accum_ for a sequence of groups of (i, j) output pairs, validated on the
+    host and then uploaded -> (goff (K + 1) int32, gent (E) int32 packed (max(i, j) << 16) | min(i, j)), device
+    tensors.  Order and duplicates are kept.  Raises ValueError for no group, an empty group, an entry that is not
+    a pair of integers, or an index outside 0..D-1."""
+    if isinstance(groups, (str, bytes)):
+        raise ValueError("groups must be a sequence of groups of (i, j) pairs")
+    try:
+        lst = [[tuple(int(v) for v in p) for p in g] for g in groups]
+    except (TypeError, ValueError):
+        raise ValueError("groups must be a sequence of groups of (i, j) pairs") from None
+    if len(lst) == 0 or any(len(g) == 0 for g in lst):
+        raise ValueError("groups: at least one group, and no empty group")
+    if any(len(p) != 2 for g in lst for p in g):
+        raise ValueError("groups: every entry must be an (i, j) pair")
+    if any(not (0 <= i < D and 0 <= j < D) for g in lst for i, j in g):
+        raise ValueError(f"groups: output indices must lie in 0..{D - 1}")
+    off = [0]
+    for g in lst:
+        off.append(off[-1] + len(g))
+    if off[-1] > 0x7fffffff:
+        raise ValueError("groups: too many entries")
+    ent = [(max(i, j) << 16) | min(i, j) for g in lst for i, j in g]
+    return (torch.tensor(off, dtype=torch.int32).to(device), torch.tensor(ent, dtype=torch.int32).to(device))
+
+
+def _check_group_args(goff, gent, C, N, S, s_off, name):
+    for nm, t in (("goff", goff), ("gent", gent)):
+        L.require_device(t, nm)
+        assert t.dtype == torch.int32 and t.dim() == 1 and t.is_contiguous(), nm
+    K, E = goff.numel() - 1, gent.numel()
+    assert K >= 1 and E >= K, "a group table holds at least one group and one entry per group"
+    L.require_device(C, name)
+    assert C.dtype == torch.float64 and C.dim() == 3 and C.shape[:2] == (K, N) and C.is_contiguous(), name
+    assert 0 <= s_off and s_off + S <= C.shape[2]
+    return K, E
+
+
+def corr_group_(pair_mu, pair_sd, z_p, goff, gent, C, s_off=0):
+    """One chunk of per-sample group means of the output correlations (csrc/cgroup.hip): C[k, n, s_off + s] is
+    written for the S samples of z_p and the K groups of the table (goff, gent) = group_table(...); nothing is
+    accumulated.  pair_mu / pair_sd (Q, N) may have a row stride; z_p (S, >= Q N) is a column range of a noise block
+    (unit column stride); C (K, N, ld_c) contiguous with ld_c >= s_off + S."""
+    for name, t in (("pair_mu", pair_mu), ("pair_sd", pair_sd), ("z_p", z_p)):
+        L.require_device(t, name)
+        assert t.dtype == torch.float64, name
+    Q, N = pair_mu.shape
+    D = int(((8 * Q + 1) ** 0.5 - 1) / 2 + 0.5)
+    assert D * (D + 1) // 2 == Q and pair_sd.shape == (Q, N)
+    assert pair_mu.stride(1) == 1 and pair_sd.stride(1) == 1 and pair_mu.stride(0) == pair_sd.stride(0) >= N
+    assert z_p.dim() == 2 and z_p.shape[1] >= Q * N and (z_p.stride(1) == 1 or z_p.shape[1] == 1)
+    S = z_p.shape[0]
+    s_off = int(s_off)
+    K, E = _check_group_args(goff, gent, C, N, S, s_off, "C")
+    z_stride = z_p.stride(0) if S > 1 else 0
+    L.check(L.lib().nmgp_corr_group_f64(L.ptr(pair_mu), L.ptr(pair_sd), pair_mu.stride(0), L.ptr(z_p), int(z_stride),
+                                        D, N, S, L.ptr(goff), L.ptr(gent), K, E, L.ptr(C), C.shape[2], s_off,
+                                        L.stream_handle()), "corr_group")
     return C
 
 

@@ -1043,17 +1043,21 @@ def sample_FY(model, x, n_sample=1000):
     return tuple(o.cpu().numpy() for o in out)
 
 
-def summarize_FY(model, x, n_sample=1000, quantiles=(0.025, 0.975), corr_pairs=None, partial=False):
+def summarize_FY(model, x, n_sample=1000, quantiles=(0.025, 0.975), corr_pairs=None, partial=False,
+                 corr_groups=None):
     """What the reference's drivers make of sample_FY (NMGP_ECoG_full.py:329-332): means and quantile bands of
     tilde_ell and Y, mean and sd of the output correlations -- a dict of numpy arrays (predict.summarize_FY; the
     (S, N, D, D) correlation samples are never stored).  corr_pairs ("all" or a sequence of (i, j)) adds
     "corr_pairs" (P, 2) and "corr_quantiles" (len(quantiles), N, P), the bands plot_corrs draws
     (code/utils.py:354-366).  partial=True adds "pcorr_mean" and "pcorr_sd" (N, D, D), mean and sd of the outputs'
     partial correlations (the normalised precision matrix of every sample), and with corr_pairs "pcorr_quantiles"
-    (len(quantiles), N, P)."""
+    (len(quantiles), N, P).  corr_groups (a sequence of K groups of (i, j) pairs, e.g. from
+    predict.groups_from_labels) adds the bands of the group-mean correlations the ECoG driver plots
+    (NMGP_ECoG_full.py:456-544): "corr_group_sizes" (K,), "corr_group_mean" and "corr_group_sd" (N, K),
+    "corr_group_quantiles" (len(quantiles), N, K), and with partial=True the same three keys with "pcorr_group_"."""
     from . import predict
     out = predict.summarize_FY(model, torch.from_numpy(np.asarray(x)).to(F64), n_sample=n_sample, quantiles=quantiles,
-                               corr_pairs=corr_pairs, partial=partial)
+                               corr_pairs=corr_pairs, partial=partial, corr_groups=corr_groups)
     return {k: v.cpu().numpy() for k, v in out.items()}
 
 

@@ -375,6 +375,71 @@ def _parse_corr_pairs(corr_pairs, D):
     return torch.tensor(lst, dtype=torch.long).reshape(len(lst), 2)
 
 
+def _parse_corr_groups(corr_groups, D):
+    """corr_groups of summarize_FY -> list of K >= 1 non-empty lists of (i, j) with 0 <= i, j < D, order and
+    duplicates kept; ValueError for anything else (an empty outer sequence, an empty group, an entry that is not a
+    pair, an index out of range, a string)."""
+    if isinstance(corr_groups, (str, bytes)):
+        raise ValueError("corr_groups must be None or a sequence of groups of (i, j) pairs, not a string")
+    try:
+        groups = [list(g) for g in corr_groups]
+        if any(isinstance(p, (str, bytes)) for g in groups for p in g):
+            raise TypeError
+        lst = [[tuple(int(v) for v in p) for p in g] for g in groups]
+        if any(float(v) != int(v) for g in groups for p in g for v in p):
+            raise TypeError
+    except (TypeError, ValueError):
+        raise ValueError("corr_groups must be None or a sequence of groups of (i, j) pairs") from None
+    if len(lst) == 0:
+        raise ValueError("corr_groups: at least one group")
+    if any(len(g) == 0 for g in lst):
+        raise ValueError("corr_groups: a group may not be empty")
+    if any(len(p) != 2 for g in lst for p in g):
+        raise ValueError("corr_groups: every entry must be an (i, j) pair")
+    if any(not (0 <= i < D and 0 <= j < D) for g in lst for i, j in g):
+        raise ValueError(f"corr_groups: output indices must lie in 0..{D - 1}")
+    return lst
+
+
+def groups_from_labels(labels, between=True):
+    """Within- and between-network groups for summarize_FY(corr_groups=...) from one hashable label per output ->
+    (groups, names).  For every label a with at least two members, in order of first appearance: the group of all
+    (i, j < i) with both outputs in a, named (a, a).  With between=True then, for every unordered pair of labels
+    a != b in the same order: the group of all (i, j < i) with one output in a and the other in b, named (a, b).
+    A label with a single member gets no within group.  When no label is a singleton and between=True, the groups
+    partition the D (D - 1) / 2 pairs."""
+    labels = list(labels)
+    order, members = [], {}
+    for i, a in enumerate(labels):
+        if a not in members:
+            members[a] = []
+            order.append(a)
+        members[a].append(i)
+    groups, names = [], []
+    for a in order:
+        if len(members[a]) >= 2:
+            groups.append([(i, j) for i in members[a] for j in members[a] if j < i])
+            names.append((a, a))
+    if between:
+        for x, a in enumerate(order):
+            for b in order[x + 1:]:
+                groups.append(sorted((max(i, j), min(i, j)) for i in members[a] for j in members[b]))
+                names.append((a, b))
+    return groups, names
+
+
+def _group_stats(Gb, qs):
+    """Mean, population sd and quantiles over the samples of the collected group means Gb (groups, N, S) ->
+    (N, groups), (N, groups), (len(qs), N, groups).  Mean and sd are taken group by group on (N, S) blocks, so
+    that their bits do not depend on how many groups share the buffer; a NaN sample makes its (n, k) NaN."""
+    means, sds = [], []
+    for k in range(Gb.shape[0]):
+        m = Gb[k].mean(1)
+        means.append(m)
+        sds.append(torch.sqrt(((Gb[k] - m.unsqueeze(1)) ** 2).mean(1)))
+    return torch.stack(means, 1), torch.stack(sds, 1), _band_quantiles(Gb, qs)
+
+
 def _band_quantiles(C, qs):
     """Quantiles along the last axis of the collected correlations C (pairs, N, S) -> (len(qs), N, pairs): the
     LDS sort of csrc/corrq.hip, or, for more samples than one workgroup sorts, torch.sort and the same
@@ -397,7 +462,7 @@ def _band_quantiles(C, qs):
 
 
 def summarize_FY(model, x, n_sample=1000, quantiles=(0.025, 0.975), noise_tape=None, keep_samples=False,
-                 corr_pairs=None, band_bytes=1 << 30, partial=False):
+                 corr_pairs=None, band_bytes=1 << 30, partial=False, corr_groups=None):
     """What the reference's drivers keep of NMGP.sample_FY (code/nmgp_dsvi.py:492-580; NMGP_ECoG_full.py:329-332):
     means and quantile bands of tilde_ell and Y, mean and population sd of the output correlations, as a dict of
     device tensors.  Same setup, chunking, noise layout and stream as sample_FY; each chunk's tail (pair samples,
@@ -424,7 +489,25 @@ def summarize_FY(model, x, n_sample=1000, quantiles=(0.025, 0.975), noise_tape=N
     kernel into a second (pairs, N, S) batch buffer of the size band_bytes allows and sorted like the correlation
     bands; the further batches run that kernel in collect-only mode.  A sample whose L has a zero or non-finite
     diagonal entry at an input (an exp that under- or overflowed) is NaN in every partial correlation at that input.
-    With partial=False nothing is launched or returned for it."""
+    With partial=False nothing is launched or returned for it.
+
+    corr_groups (a sequence of K >= 1 non-empty groups of (i, j) pairs, e.g. from groups_from_labels) adds what the
+    reference's ECoG driver plots (NMGP_ECoG_full.py:456-544): the correlations averaged over groups of pairs.  Per
+    sample and input the group value is the plain mean of the group's correlations -- order and duplicates kept (a
+    pair listed twice counts twice), (i, j) = (j, i), (i, i) exactly 1 where finite, groups may overlap -- of the
+    very samples whose mean is corr_mean.  Keys: "corr_group_sizes" (K,) int64, "corr_group_mean" and
+    "corr_group_sd" (N, K; population sd over the samples), "corr_group_quantiles" (len(quantiles), N, K; exact,
+    sorted like the pair bands); with partial=True also "pcorr_group_mean" / "pcorr_group_sd" /
+    "pcorr_group_quantiles" of the group means of the samples' partial correlations; with keep_samples=True also
+    "corr_group_samples" (K, N, S) (and "pcorr_group_samples"), from which any contrast between groups or inputs
+    can be formed.  A group that contains a NaN correlation at (s, n) is NaN there, and then so are that (n, k)'s
+    mean, sd and quantiles.  The reduction over the pairs happens next to the correlation matrix in LDS
+    (csrc/cgroup.hip; for the partial correlations inside csrc/pcorr.hip), one more launch per chunk; only the
+    (groups, N, S) group samples are stored.  The groups are taken in batches of max(1, band_bytes // (8 S N)),
+    independently of the pair batches: the first rides along with the summary's chunks, every further batch walks
+    the noise stream again and launches only the group kernels.  The result does not depend on band_bytes.  With
+    keep_samples=True the buffer is the full (K, N, S), whatever band_bytes says.  Anything else than None or such
+    a sequence raises ValueError before any device work; with None nothing is launched or returned."""
     qs = [float(q) for q in quantiles]
     if any(not 0.0 <= q <= 1.0 for q in qs):
         raise ValueError("quantiles must lie in [0, 1]")
@@ -432,6 +515,7 @@ def summarize_FY(model, x, n_sample=1000, quantiles=(0.025, 0.975), noise_tape=N
     if n_sample < 1:
         raise ValueError("n_sample must be at least 1")
     pairs_t = None if corr_pairs is None else _parse_corr_pairs(corr_pairs, model.D)
+    groups = None if corr_groups is None else _parse_corr_groups(corr_groups, model.D)
     dev = model.device_
     x = torch.as_tensor(x).reshape(-1, 1).to(F64).to(dev).contiguous()
     st = _sampling_setup(model, x)
@@ -462,6 +546,16 @@ def summarize_FY(model, x, n_sample=1000, quantiles=(0.025, 0.975), noise_tape=N
         if partial:
             Pb = torch.empty(pb, N, n_sample, dtype=F64, device=dev)
             pq = torch.empty(len(qs), N, P, dtype=F64, device=dev)
+    K = 0 if groups is None else len(groups)
+    if K:
+        # groups per batch; the kept samples are one buffer of all the groups
+        gb = K if keep_samples else min(K, max(1, int(band_bytes) // (8 * n_sample * N)))
+        tabs = [H.group_table(groups[k0:k0 + gb], D, dev) for k0 in range(0, K, gb)]
+        Gb = torch.empty(gb, N, n_sample, dtype=F64, device=dev)
+        gstats = [[], [], []]                                            # mean, sd, quantiles, batch by batch
+        if partial:
+            PGb = torch.empty(gb, N, n_sample, dtype=F64, device=dev)
+            pgstats = [[], [], []]
     done = 0
     while done < n_sample:
         S = min(chunk, n_sample - done)
@@ -472,11 +566,14 @@ def summarize_FY(model, x, n_sample=1000, quantiles=(0.025, 0.975), noise_tape=N
                     Ys[done:done + S], csum, csq, ws=ws)
         if P:
             H.corr_collect_(st["pair_mu"], st["pair_sd"], zc[:, o_p:], pi[:pb], pj[:pb], Cb, s_off=done)
-        if partial and P:
-            H.pcorr_accum_(st["pair_mu"], st["pair_sd"], zc[:, o_p:], psum, psq, pi[:pb], pj[:pb], Pb, s_off=done,
-                           ws=pws)
-        elif partial:
-            H.pcorr_accum_(st["pair_mu"], st["pair_sd"], zc[:, o_p:], psum, psq, ws=pws)
+        if K:
+            H.corr_group_(st["pair_mu"], st["pair_sd"], zc[:, o_p:], tabs[0][0], tabs[0][1], Gb, s_off=done)
+        if partial:
+            # one launch: L^-1 and Omega once, for the sums, the pair list and the groups
+            kw = {"pi": pi[:pb], "pj": pj[:pb], "C": Pb, "s_off": done} if P else {}
+            if K:
+                kw.update(goff=tabs[0][0], gent=tabs[0][1], Cg=PGb, sg_off=done)
+            H.pcorr_accum_(st["pair_mu"], st["pair_sd"], zc[:, o_p:], psum, psq, ws=pws, **kw)
         done += S
     mean = csum / n_sample
     out = {"tilde_ell_mean": Ts.mean(0), "tilde_ell_quantiles": _quantiles_dim0(Ts, qs),
@@ -518,6 +615,38 @@ def summarize_FY(model, x, n_sample=1000, quantiles=(0.025, 0.975), noise_tape=N
         out["corr_pairs"], out["corr_quantiles"] = pairs_t.to(dev), cq
         if partial:
             out["pcorr_quantiles"] = pq
+    if K:
+        G = T = zc = None
+        o_p = M + N                                                       # the noise layout of _sample_TG
+        for b, (goff, gent) in enumerate(tabs):
+            kb = goff.numel() - 1
+            if b > 0:
+                draws.rewind()
+                done = 0
+                while done < n_sample:
+                    S = min(chunk, n_sample - done)
+                    zc = draws.take(S, per)
+                    H.corr_group_(st["pair_mu"], st["pair_sd"], zc[:, o_p:], goff, gent, Gb[:kb], s_off=done)
+                    if partial:
+                        H.pcorr_accum_(st["pair_mu"], st["pair_sd"], zc[:, o_p:], goff=goff, gent=gent, Cg=PGb[:kb],
+                                       sg_off=done)
+                    done += S
+                    del zc
+            for acc, v in zip(gstats, _group_stats(Gb[:kb], qs)):
+                acc.append(v)
+            if partial:
+                for acc, v in zip(pgstats, _group_stats(PGb[:kb], qs)):
+                    acc.append(v)
+        out["corr_group_sizes"] = torch.tensor([len(g) for g in groups], dtype=torch.long, device=dev)
+        out["corr_group_mean"], out["corr_group_sd"] = torch.cat(gstats[0], 1), torch.cat(gstats[1], 1)
+        out["corr_group_quantiles"] = torch.cat(gstats[2], 2)
+        if partial:
+            out["pcorr_group_mean"], out["pcorr_group_sd"] = torch.cat(pgstats[0], 1), torch.cat(pgstats[1], 1)
+            out["pcorr_group_quantiles"] = torch.cat(pgstats[2], 2)
+        if keep_samples:
+            out["corr_group_samples"] = Gb
+            if partial:
+                out["pcorr_group_samples"] = PGb
     return out
 
 

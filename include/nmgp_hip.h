@@ -755,6 +755,48 @@ int nmgp_pcorr_accum_f64(const double* pair_mu, const double* pair_sd, int64_t l
                          const int32_t* pj, int P, double* C, int64_t ld_c, int64_t s_off, void* ws, int64_t ws_bytes,
                          hipStream_t stream);
 
+/* Group means of the output correlations (reference NMGP_ECoG_full.py:456-544, "Post analysis": the correlations
+ * averaged over the neighbour and distance groups of the electrode grid) and of the partial correlations, per
+ * sample, without the (S, N, D, D) tensor and without per-pair samples.  fp64.
+ *
+ * The group table is a CSR in DEVICE memory (a launch can be captured): goff, K + 1 int32 offsets into the entries
+ * (goff[0] = 0, goff[K] = E), and gent, E int32 entries (max(i, j) << 16) | min(i, j).  Order and duplicates count
+ * (a pair listed twice weighs twice), groups may overlap, (i, i) is the diagonal value.  The table cannot be
+ * validated on the host, and it cannot make the kernel leave its buffers: offsets are clamped to 0..E and made
+ * monotone (a group left empty is 0 / 0 = NaN), an entry outside 0..D-1 is NaN and so is its group, the other
+ * groups are not affected.
+ *
+ * nmgp_corr_group_f64: for every group k < K, input n < N and sample s < S of this chunk, with corr the correlation
+ * of nmgp_fy_accum_f64 (the same L, the same MFMA order, the same normalisation acc * isi * isj, the diagonal
+ * exactly 1 where finite, non-finite values kept: a group of one pair is that correlation bit for bit),
+ *   C[(k * N + n) * ld_c + s_off + s] = (sum_{e in group k} corr[s, n, i_e, j_e]) / |group k|.
+ * A group with a NaN correlation at (s, n) is NaN at (s, n).  The sum is taken in float64 in an order that is a
+ * function of the group alone -- up to 256 entries: lane l of one wave adds the entries l, l + 64, ..., then a xor
+ * butterfly over the lanes; longer: thread t of the workgroup adds the entries t, t + 256, ..., a butterfly per
+ * wave, the 4 wave sums added in wave order -- so C does not depend on the other groups of the call, on how the
+ * samples are split over calls (s_off) or over slices, nor on the run: no atomics, no workspace, every element of the
+ * addressed columns written exactly once, the other columns of a wider C left alone.  One workgroup per (input,
+ * slice of samples) with L and the normalised triangle in LDS (2 x 72 KiB + 1 KiB at D = 128).  Returns 0 and
+ * launches nothing when K, N or S is 0, NMGP_ERR_CGROUP_ARG before any launch when D is outside 1..128, N, S, K or
+ * s_off is negative, a pointer is NULL, E < K, ld_pair < N, z_stride < 0 or ld_c < s_off + S.
+ *
+ * nmgp_pcorr_accum_groups_f64: nmgp_pcorr_accum_f64 with a third, independent output next to the sums and the pair
+ * list: Cg[(k * N + n) * ld_cg + sg_off + s] = the group means of that sample's partial correlations (the values
+ * the pair list collects; NaN everywhere where the sample is NaN), by the same reduction.  K = 0 is
+ * nmgp_pcorr_accum_f64 exactly (which forwards here); sums and C have the same bits with and without groups, Cg
+ * the same bits with and without sums and pair list.  Refused (NMGP_ERR_PCORR_ARG) as nmgp_pcorr_accum_f64, and
+ * when sums, pair list and groups are all absent, K or sg_off is negative, or K > 0 and goff, gent or Cg is NULL,
+ * E < K or ld_cg < sg_off + S.                                                                                  */
+#define NMGP_ERR_CGROUP_ARG (-64)
+int nmgp_corr_group_f64(const double* pair_mu, const double* pair_sd, int64_t ld_pair, const double* z_p,
+                        int64_t z_stride, int D, int N, int S, const int32_t* goff, const int32_t* gent, int K,
+                        int E, double* C, int64_t ld_c, int64_t s_off, hipStream_t stream);
+int nmgp_pcorr_accum_groups_f64(const double* pair_mu, const double* pair_sd, int64_t ld_pair, const double* z_p,
+                                int64_t z_stride, int D, int N, int S, double* pc_sum, double* pc_sq,
+                                const int32_t* pi, const int32_t* pj, int P, double* C, int64_t ld_c, int64_t s_off,
+                                const int32_t* goff, const int32_t* gent, int K, int E, double* Cg, int64_t ld_cg,
+                                int64_t sg_off, void* ws, int64_t ws_bytes, hipStream_t stream);
+
 /* Whole-step HIP graphs (the reference runs its step eagerly, code/nmgp_dsvi.py:829-854; the build captures
  * noise -> forward -> backward -> Adam once and replays it).  Capture goes straight through the HIP runtime:
  * begin on `stream` (thread-local mode; other streams join through event waits and must join back before
