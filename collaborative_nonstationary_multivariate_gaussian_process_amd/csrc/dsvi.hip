@@ -16,6 +16,7 @@
 // One wave (64 lanes) per minibatch row: lanes stride over the M inducing columns and reduce
 // with xor-shuffles; per-output quantities live one per lane (lane d, register d>>6).
 #include "common.hpp"
+#include "step_begin.hpp"
 
 namespace nmgp {
 
@@ -1388,39 +1389,6 @@ __global__ __launch_bounds__(1024) void batch_gather_kernel(const T* Xb, const T
   if (threadIdx.x == 0) ctr[0] += 1;
 }
 
-// ------------------------------------------------------------------------------------ Philox
-__device__ inline void philox_round(uint32_t (&c)[4], uint32_t (&k)[2]) {
-  const uint64_t p0 = (uint64_t)0xD2511F53u * c[0];
-  const uint64_t p1 = (uint64_t)0xCD9E8D57u * c[2];
-  const uint32_t h0 = (uint32_t)(p0 >> 32), l0 = (uint32_t)p0;
-  const uint32_t h1 = (uint32_t)(p1 >> 32), l1 = (uint32_t)p1;
-  c[0] = h1 ^ c[1] ^ k[0];
-  c[1] = l1;
-  c[2] = h0 ^ c[3] ^ k[1];
-  c[3] = l0;
-  k[0] += 0x9E3779B9u;
-  k[1] += 0xBB67AE85u;
-}
-
-// normals 4t .. 4t+3 of the Philox-4x32-10 stream (key = seed, counter = (t, base)), Box-Muller
-template <typename T>
-__device__ inline void normal_quad(T* out, int64_t n, uint64_t seed, uint64_t base, int64_t t) {
-  uint32_t c[4] = {(uint32_t)t, (uint32_t)((uint64_t)t >> 32), (uint32_t)base, (uint32_t)(base >> 32)};
-  uint32_t k[2] = {(uint32_t)seed, (uint32_t)(seed >> 32)};
-#pragma unroll
-  for (int r = 0; r < 10; ++r) philox_round(c, k);
-  const double inv = 2.3283064365386963e-10;   // 2^-32
-  double u[4];
-#pragma unroll
-  for (int q = 0; q < 4; ++q) u[q] = ((double)c[q] + 0.5) * inv;
-  const double two_pi = 6.283185307179586;
-  const double r0 = sqrt(-2.0 * log(u[0])), r1 = sqrt(-2.0 * log(u[2]));
-  double z[4] = {r0 * cos(two_pi * u[1]), r0 * sin(two_pi * u[1]), r1 * cos(two_pi * u[3]), r1 * sin(two_pi * u[3])};
-#pragma unroll
-  for (int q = 0; q < 4; ++q)
-    if (t * 4 + q < n) out[t * 4 + q] = (T)z[q];
-}
-
 template <typename T>
 __global__ void normal_kernel(T* out, int64_t n, uint64_t seed, const int64_t* counter, int64_t offset) {
   const int64_t t = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
@@ -1439,37 +1407,8 @@ __global__ __launch_bounds__(256) void step_begin_kernel(const T* Xb, const T* Y
                                                          int64_t* bctr, T* x, T* y, int32_t* ro, int32_t* seg,
                                                          T* noise, int64_t nnoise, uint64_t seed, int64_t* nctr,
                                                          int32_t* done, T* grad, int64_t ngrad) {
-  const uint64_t base = (uint64_t)nctr[0];
-  const int64_t tid = (int64_t)blockIdx.x * blockDim.x + threadIdx.x, stride = (int64_t)gridDim.x * blockDim.x;
-  for (int64_t q = tid; q * 4 < nnoise; q += stride) normal_quad<T>(noise, nnoise, seed, base, q);
-  if ((((uintptr_t)grad) & 15) == 0) {      // 16-byte stores
-    constexpr int V = 16 / (int)sizeof(T);
-    struct alignas(16) Z { T e[V]; };
-    const Z z{};
-    const int64_t nv = ngrad / V;
-    for (int64_t i = tid; i < nv; i += stride) ((Z*)grad)[i] = z;
-    for (int64_t i = nv * V + tid; i < ngrad; i += stride) grad[i] = (T)0;
-  } else {
-    for (int64_t i = tid; i < ngrad; i += stride) grad[i] = (T)0;
-  }
-  if (blockIdx.x == 0) {
-    const int64_t b = bctr[0] % nbatch;
-    for (int64_t i = threadIdx.x; i < B; i += blockDim.x) {
-      x[i] = Xb[b * B + i];
-      y[i] = Yb[b * B + i];
-      ro[i] = Ib[b * B + i];
-    }
-    for (int64_t i = threadIdx.x; i < nseg; i += blockDim.x) seg[i] = Sb[b * nseg + i];
-  }
-  __syncthreads();
-  if (threadIdx.x == 0) {
-    if (blockIdx.x == 0) bctr[0] += 1;
-    const int old = __hip_atomic_fetch_add(done, 1, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-    if (old == (int)gridDim.x - 1) {
-      nctr[0] += 1;
-      __hip_atomic_store(done, 0, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-    }
-  }
+  step_begin_body<T>(BeginArgs<T>{Xb, Yb, Ib, Sb, B, nseg, nbatch, bctr, x, y, ro, seg, noise, nnoise, seed, nctr, done, grad, ngrad},
+                     (int)blockIdx.x, (int)gridDim.x);
 }
 
 static inline unsigned blocks_rows(int B) { return (unsigned)((B + 3) / 4); }

@@ -194,6 +194,9 @@ class DsviEngine:
                         and os.environ.get("NMGP_FUSE_TP", "1") != "0")
         # and the Gibbs prior's K22 from the first of them (NMGP_FUSE_VG=0: its own launch, dsvi_vg22)
         self.fuse_vg = self.fuse_tp and os.environ.get("NMGP_FUSE_VG", "1") != "0"
+        # and a bound dataset's step starts with ONE launch, nmgp_step_head_*: step_begin, the RBF K22 builders and
+        # Sigma_v as workgroups of one grid (NMGP_FUSE_HEAD=0: the three launches; the tests' equivalence switch)
+        self.fuse_head = self.fuse_tp and os.environ.get("NMGP_FUSE_HEAD", "1") != "0"
         # per-(output, factor) L-bar products of the grouped backward (bwd_lbar), summed by nmgp_lbar_reduce: D(D+1)/2
         # slots of M x M + M.  Only where the slots stay small (PM2.5: 15 slots, 7.9 MB); many outputs with few
         # rows each (HCP-like D = 50) keep one product per factor, whose k loop is then short anyway
@@ -852,12 +855,47 @@ class DsviEngine:
             self.noise.numel(), ctypes.c_uint64(seed), vp(counter.data_ptr()), vp(self._begin_done.data_ptr()),
             vp(self._grad.data_ptr()), self._grad.numel(), s), "step_begin")
 
+    def head_groups(self):
+        """The pairwise group (RBF K22 + lam I) and the grouped GEMM (Sigma_v + lam I) that nmgp_step_head_* runs
+        beside step_begin, or None where the step keeps its three launches: the head kernel walks a plain
+        latency-kernel launch (no device tile plan, not the persistent form)."""
+        if not self.fuse_head:
+            return None
+        p = self._plan(0)
+        k22, sy = p.get("build_k22"), p.get("syrk")
+        if k22 is None or not isinstance(sy, H.GemmGroup) or not sy.lat or sy.pipe or sy.plan is not None:
+            return None
+        if k22.total <= 0 or sy.total <= 0:
+            return None
+        return k22, sy
+
+    def head_step(self, seed, counter, stream=None):
+        """begin_step + p["build_k22"] + p["syrk"] in one launch (nmgp_step_head_*; same values bit for bit)."""
+        k22, sy = self.head_groups()
+        Xb, Yb, Ib, Sb, ctr = self._dataset
+        if getattr(self, "_begin_done", None) is None:
+            self._begin_done = torch.zeros(1, dtype=torch.int32, device=self.dev)
+        s = L.stream_handle() if stream is None else stream
+        vp = ctypes.c_void_p
+        L.check(getattr(L.lib(), "nmgp_step_head_" + self.sfx)(
+            *(vp(t.data_ptr()) for t in (Xb, Yb, Ib, Sb)), self.B, self.D + 1, Xb.shape[0], vp(ctr.data_ptr()),
+            *(vp(t.data_ptr()) for t in (self.x, self.y, self.row_out, self.seg)), vp(self.noise.data_ptr()),
+            self.noise.numel(), ctypes.c_uint64(seed), vp(counter.data_ptr()), vp(self._begin_done.data_ptr()),
+            vp(self._grad.data_ptr()), self._grad.numel(), vp(k22.dev.data_ptr()), k22.n, k22.total,
+            vp(sy.dev.data_ptr()), sy.n, sy.total, vp(sy.seg.data_ptr()) if sy.seg is not None else None, s),
+            "step_head")
+
     def begin_forward_backward(self, seed, counter):
-        """begin_step + forward_backward(zero_grad=False), back to back on the current stream.  (Round 3 measured
-        the step-begin launch on its own stream beside the theta-only head of the forward chain: bit-identical,
-        6% slower -- profiles/r03zh_early_begin_ab.txt.)"""
-        self.begin_step(seed, counter)
-        return self.forward_backward(zero_grad=False)
+        """The step's first launch and forward_backward(zero_grad=False), back to back on the current stream: head_step
+        with the schedule that leaves the K22 and Sigma_v launches out, else begin_step.  (Round 3 measured the
+        step-begin launch on its own stream beside the theta-only head of the forward chain: bit-identical, 6%
+        slower for its cross-queue hops -- profiles/r03zh_early_begin_ab.txt; one launch has no hop.)"""
+        head = self.head_groups() is not None
+        if head:
+            self.head_step(seed, counter)
+        else:
+            self.begin_step(seed, counter)
+        return self.forward_backward(zero_grad=False, head=head)
 
     def device_noise(self, seed, counter):
         H.normal_(self.noise, seed, counter=counter)   # dtype-dispatched Philox normals
@@ -1298,15 +1336,24 @@ class DsviEngine:
             else:
                 fn(handles[where])
 
-    def forward_backward(self, stream=None, timer=None, zero_grad=True):
-        """Enqueue -SELBO (self.out[0]) and all gradients (into the bound grad vector)."""
+    def _head_schedule(self, steps):
+        """`steps` for a step that head_step began: without the K22 and Sigma_v launches (same closures, same argument
+        struct).  The capture order stays: the side stream's first launch, then the first fused factorization on main.
+        Capturing the factorization first, as the head's first child, was 27% slower (0.656 -> 0.833 ms,
+        profiles/r07a_head_ab.txt; measured, the cause not looked into)."""
+        return [it for it in steps if it[0] not in ("build_k22", "syrk")]
+
+    def forward_backward(self, stream=None, timer=None, zero_grad=True, head=False):
+        """Enqueue -SELBO (self.out[0]) and all gradients (into the bound grad vector); head: the step was begun by
+        head_step, which formed K22 + lam I and Sigma_v + lam I already."""
         key = ("fb", self._theta.data_ptr(), self._grad.data_ptr(), self.frozen_mask, self.N)
         if getattr(self, "_sched_key", None) != key:
             self._sched = self._schedule(0)
+            self._sched_head = self._head_schedule(self._sched)
             self._sched_key = key
         if zero_grad:
             self._grad.zero_()
-        self._run(self._sched, stream, timer)
+        self._run(self._sched_head if head else self._sched, stream, timer)
         return self.out
 
     def elbo_sample(self, stream=None, with_kl=False, cached=False, kl_part=None):

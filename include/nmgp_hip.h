@@ -624,6 +624,22 @@ int nmgp_step_begin_f32(const float* Xb, const float* Yb, const int32_t* Ib, con
                         int64_t nseg, int64_t nbatch, int64_t* bctr, float* x, float* y, int32_t* row_out,
                         int32_t* seg, float* noise, int64_t nnoise, uint64_t seed, int64_t* nctr, int32_t* done,
                         float* grad, int64_t ngrad, hipStream_t stream);
+/* The same start of a step together with two theta-only launches of the fused-prior schedule, in ONE launch: the
+ * pairwise group pw (npd descriptors, pw_tiles tiles: the RBF K22 + lam I; as nmgp_pairwise_*) and the grouped GEMM gd
+ * (ngd descriptors, lat_tiles tiles, laid out for nmgp_gemm_grouped_lat_* WITHOUT a device tile plan: Sigma_v + lam I;
+ * lat_seg: its segment table or NULL) run as further workgroups of the grid, each exactly as in its own launch.
+ * Neither may read what the begin part writes (minibatch, noise, gradient).  Error codes as nmgp_step_begin_*, then
+ * -20 pw / npd / pw_tiles, -23 gd / ngd / lat_tiles missing or not positive.                                      */
+int nmgp_step_head_f64(const double* Xb, const double* Yb, const int32_t* Ib, const int32_t* Sb, int64_t B,
+                       int64_t nseg, int64_t nbatch, int64_t* bctr, double* x, double* y, int32_t* row_out,
+                       int32_t* seg, double* noise, int64_t nnoise, uint64_t seed, int64_t* nctr, int32_t* done,
+                       double* grad, int64_t ngrad, const nmgp_pairwise_desc* pw, int npd, int pw_tiles,
+                       const nmgp_gemm_desc* gd, int ngd, int lat_tiles, const int32_t* lat_seg, hipStream_t stream);
+int nmgp_step_head_f32(const float* Xb, const float* Yb, const int32_t* Ib, const int32_t* Sb, int64_t B,
+                       int64_t nseg, int64_t nbatch, int64_t* bctr, float* x, float* y, int32_t* row_out,
+                       int32_t* seg, float* noise, int64_t nnoise, uint64_t seed, int64_t* nctr, int32_t* done,
+                       float* grad, int64_t ngrad, const nmgp_pairwise_desc* pw, int npd, int pw_tiles,
+                       const nmgp_gemm_desc* gd, int ngd, int lat_tiles, const int32_t* lat_seg, hipStream_t stream);
 int nmgp_batch_gather_f64(const double* Xb, const double* Yb, const int32_t* Ib, const int32_t* Sb, int64_t B,
                           int64_t nseg, int64_t nbatch, int64_t* batch_counter, double* x, double* y,
                           int32_t* row_out, int32_t* seg, hipStream_t stream);
