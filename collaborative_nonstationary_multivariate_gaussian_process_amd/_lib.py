@@ -240,6 +240,10 @@ _SIGS = {
     "nmgp_pcorr_accum_groups_f64": (c_int, [c_vp, c_vp, c_i64, c_vp, c_i64, c_int, c_int, c_int, c_vp, c_vp, c_vp,
                                             c_vp, c_int, c_vp, c_i64, c_i64, c_vp, c_vp, c_int, c_int, c_vp, c_i64,
                                             c_i64, c_vp, c_i64, c_vp]),
+    "nmgp_ycond_workspace_size": (c_i64, [c_int, c_int, c_int]),
+    "nmgp_ycond_accum_f64": (c_int, [c_vp, c_vp, c_i64, c_vp, c_i64, c_vp, c_vp, c_vp, c_dbl, c_int, c_int, c_int,
+                                     c_vp, c_int, c_vp, c_vp, c_vp, c_vp, c_vp, c_vp, c_vp, c_vp, c_i64, c_i64, c_vp,
+                                     c_i64, c_vp]),
     "nmgp_counter_add": (c_int, [c_vp, c_i64, c_vp]),
     "nmgp_pbar_reduce_f64": (c_int, [c_vp, c_i64, c_vp, c_i64, c_vp, c_int, c_int, c_int, c_vp]),
     "nmgp_pbar_reduce_f32": (c_int, [c_vp, c_i64, c_vp, c_i64, c_vp, c_int, c_int, c_int, c_vp]),

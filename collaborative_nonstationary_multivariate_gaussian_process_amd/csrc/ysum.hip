@@ -16,6 +16,7 @@
 #include <math.h>
 
 #include "common.hpp"
+#include "lse_state.hpp"
 
 namespace nmgp {
 
@@ -31,23 +32,6 @@ static int y_slices(int D, int N, int S) {
   int64_t want = waves > kYFill / 2 ? 1 : kYFill / waves;
   if (want > S) want = S;
   return (int)(want < 1 ? 1 : want);
-}
-
-// (m, r) <- log-sum-exp state of two states: M = max, r = r1 exp(m1 - M) + r2 exp(m2 - M).  Two empty states
-// (-inf, 0) stay empty (exp(-inf - -inf) would be NaN); a NaN in either makes both words NaN.
-__device__ inline void y_lse_combine(double m1, double r1, double m2, double r2, double* m, double* r) {
-  if (m1 != m1 || m2 != m2 || r1 != r1 || r2 != r2) {
-    *m = *r = __builtin_nan("");
-    return;
-  }
-  const double M = fmax(m1, m2);
-  if (M == -INFINITY) {
-    *m = -INFINITY;
-    *r = 0.0;
-    return;
-  }
-  *m = M;
-  *r = r1 * exp(m1 - M) + r2 * exp(m2 - M);
 }
 
 __global__ __launch_bounds__(kYLanes* kYRows) void y_rows_kernel(

@@ -1251,6 +1251,78 @@ def pcorr_accum_(pair_mu, pair_sd, z_p, pc_sum=None, pc_sq=None, pi=None, pj=Non
     return C
 
 
+def ycond_workspace(D, N, S, device):
+    """Workspace of ycond_accum_ for chunks of up to S samples (the slices' partial sums), or None when the samples
+    are not sliced (N >= 256 or S == 1)."""
+    # as pcorr_workspace: a shorter last chunk can be cut into more slices than a full one
+    need = max(L.lib().nmgp_ycond_workspace_size(D, N, s) for s in {S, min(S, max(1, 512 // max(N, 1)))})
+    return torch.empty(need, dtype=torch.uint8, device=device) if need > 0 else None
+
+
+def missing_table(Y_obs):
+    """The entry table of ycond_accum_ for Y_obs (N, D): e_off (N + 1) int32, the prefix sum of the rows' counts of
+    non-finite entries, and missing (E, 2) int64, their (n, d) in row-major order.  Device tensors."""
+    miss = ~torch.isfinite(Y_obs)
+    e_off = torch.zeros(Y_obs.shape[0] + 1, dtype=torch.int32, device=Y_obs.device)
+    e_off[1:] = torch.cumsum(miss.sum(1), 0).to(torch.int32)
+    return e_off, torch.nonzero(miss)
+
+
+def ycond_accum_(pair_mu, pair_sd, z_p, mu_g, var_g, Y_obs, s2, e_off, mu_sum, y2_sum, f2_sum, y_true=None,
+                 lse_max=None, lse_sum=None, Mu=None, Var=None, s_off=0, ws=None):
+    """One chunk of the fused conditional prediction of the missing outputs (csrc/ycond.hip): per sample and input
+    A = V^-1 + L^T diag(w) L, its tiled Cholesky and the forward solves, for every missing entry of Y_obs (N, D;
+    non-finite = missing) the conditional mean mu and variance v given the observed outputs of the same input.
+    pair_mu / pair_sd / z_p as pcorr_accum_; mu_g / var_g (S, N, D) contiguous; s2 the noise variance, jitter
+    included; e_off = missing_table(Y_obs)[0].  mu_sum / y2_sum / f2_sum (E,) are accumulated onto (sum of mu, of
+    v + mu^2, of v - s2 + mu^2); with y_true (E,) the log-sum-exp state lse_max / lse_sum (E,; started at -inf / 0)
+    of log N(y_true | mu, v) is advanced where y_true is finite; with Mu / Var (ld >= s_off + S, E) the samples'
+    mu and v are written to row s_off + s.  ws: ycond_workspace(...) kept by a caller that runs several chunks,
+    else allocated here."""
+    for name, t in (("pair_mu", pair_mu), ("pair_sd", pair_sd), ("z_p", z_p), ("mu_g", mu_g), ("var_g", var_g),
+                    ("Y_obs", Y_obs), ("mu_sum", mu_sum), ("y2_sum", y2_sum), ("f2_sum", f2_sum)):
+        L.require_device(t, name)
+        assert t.dtype == torch.float64, name
+    Q, N = pair_mu.shape
+    D = int(((8 * Q + 1) ** 0.5 - 1) / 2 + 0.5)
+    assert D * (D + 1) // 2 == Q and pair_sd.shape == (Q, N)
+    assert pair_mu.stride(1) == 1 and pair_sd.stride(1) == 1 and pair_mu.stride(0) == pair_sd.stride(0) >= N
+    assert z_p.dim() == 2 and z_p.shape[1] >= Q * N and (z_p.stride(1) == 1 or z_p.shape[1] == 1)
+    S = z_p.shape[0]
+    z_stride = z_p.stride(0) if S > 1 else 0
+    for name, t in (("mu_g", mu_g), ("var_g", var_g)):
+        assert t.shape == (S, N, D) and t.is_contiguous(), name
+    assert Y_obs.shape == (N, D) and Y_obs.is_contiguous()
+    L.require_device(e_off, "e_off")
+    assert e_off.dtype == torch.int32 and e_off.shape == (N + 1,) and e_off.is_contiguous()
+    E = mu_sum.numel()
+    for name, t in (("mu_sum", mu_sum), ("y2_sum", y2_sum), ("f2_sum", f2_sum)):
+        assert t.shape == (E,) and t.is_contiguous(), name
+    assert (y_true is None) == (lse_max is None) == (lse_sum is None), "y_true, lse_max and lse_sum go together"
+    if y_true is not None:
+        for name, t in (("y_true", y_true), ("lse_max", lse_max), ("lse_sum", lse_sum)):
+            L.require_device(t, name)
+            assert t.dtype == torch.float64 and t.shape == (E,) and t.is_contiguous(), name
+    assert (Mu is None) == (Var is None), "Mu and Var go together"
+    ld, s_off = 0, int(s_off)
+    if Mu is not None:
+        for name, t in (("Mu", Mu), ("Var", Var)):
+            L.require_device(t, name)
+            assert t.dtype == torch.float64 and t.dim() == 2 and t.shape[1] == E and t.is_contiguous(), name
+        ld = Mu.shape[0]
+        assert Var.shape[0] == ld and 0 <= s_off and s_off + S <= ld
+    lib = L.lib()
+    need = lib.nmgp_ycond_workspace_size(D, N, S) if E > 0 else 0
+    if need > 0 and (ws is None or ws.numel() * ws.element_size() < need):
+        ws = torch.empty(need, dtype=torch.uint8, device=z_p.device)                    # slices' partial sums
+    L.check(lib.nmgp_ycond_accum_f64(L.ptr(pair_mu), L.ptr(pair_sd), pair_mu.stride(0), L.ptr(z_p), int(z_stride),
+                                     L.ptr(mu_g), L.ptr(var_g), L.ptr(Y_obs), float(s2), D, N, S, L.ptr(e_off), E,
+                                     L.ptr(mu_sum), L.ptr(y2_sum), L.ptr(f2_sum), L.ptr(y_true), L.ptr(lse_max),
+                                     L.ptr(lse_sum), L.ptr(Mu), L.ptr(Var), ld, s_off,
+                                     L.ptr(ws) if need > 0 else None, need, L.stream_handle()), "ycond_accum")
+    return mu_sum
+
+
 def group_table(groups, D, device):
     """The CSR table of corr_group_ / pcorr_accum_ for a sequence of groups of (i, j) output pairs, validated on the
     host and then uploaded -> (goff (K + 1) int32, gent (E) int32 packed (max(i, j) << 16) | min(i, j)), device

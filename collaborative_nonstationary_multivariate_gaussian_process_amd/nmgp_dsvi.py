@@ -1072,6 +1072,18 @@ def summarize_Y(model, X_list, Y_list=None, n_sample=1000, index=None, quantiles
     return {k: v.cpu().numpy() for k, v in out.items()}
 
 
+def impute_Y(model, x, Y_obs, Y_true=None, n_sample=1000, quantiles=(0.025, 0.975)):
+    """The missing outputs at the inputs x predicted from the outputs observed at the same inputs (Y_obs (N, D),
+    NaN where missing; predict.observed_grid builds it from per-output lists): mixture mean, sd and quantile bands
+    per missing entry and, with Y_true, log predictive density, RMSE and coverage -- a dict of numpy arrays
+    (predict.impute_Y; one fused launch per chunk, no (S, N, D, D) tensor)."""
+    from . import predict
+    out = predict.impute_Y(model, torch.from_numpy(np.asarray(x, np.float64)), np.asarray(Y_obs, np.float64),
+                           None if Y_true is None else np.asarray(Y_true, np.float64), n_sample=n_sample,
+                           quantiles=quantiles)
+    return {k: v.cpu().numpy() for k, v in out.items()}
+
+
 def predict_Y(model, X_list):
     """code/nmgp_dsvi.py:927-930 (numpy output)."""
     X_list = [torch.from_numpy(np.asarray(x)).to(F64) for x in X_list]

@@ -231,10 +231,11 @@ def _sampling_setup(model, x):
     return st
 
 
-def _sample_TG(st, zc):
-    """The part of a chunk that sample_Y, sample_FY and summarize_FY share: tilde-ell T (S, N) and the latent
-    G (S, D, N) of S samples from their noise block zc (S, per-sample noise, laid out [z_v M][z_t N][z_p Q N]
-    [z_g D N][z_f ...]).  Also returns the column offsets of z_p and z_f in zc."""
+def _sample_T_moments(st, zc):
+    """The part of a chunk that every sampler shares up to the latent's marginals: tilde-ell T (S, N) and, given it,
+    the MGP_d marginals of the latent G, mu_g (S, N, D) and var_g (S, D, N), of S samples from their noise block zc
+    (S, per-sample noise, laid out [z_v M][z_t N][z_p Q N][z_g D N][z_f ...]).  Also returns the column offsets of
+    z_p, z_g and z_f in zc."""
     N, D, M = st["N"], st["D"], st["M"]
     Q = len(st["pairs"])
     S = zc.shape[0]
@@ -242,7 +243,7 @@ def _sample_TG(st, zc):
     z_v = zc[:, o:o + M]; o += M
     z_t = zc[:, o:o + N]; o += N
     o_p = o; o += Q * N
-    z_g = zc[:, o:o + D * N].reshape(S, D, N); o += D * N
+    o_g = o; o += D * N
     o_f = o
     # v = mu_v + chol(Sigma_v + 1e-4 I) z_v ; t = P_t v + sqrt(var_t + 1e-4) z_t   (JGP_S)
     V = st["mu_v"].reshape(1, M) + H.matmul(z_v.contiguous(), st["Cv"], transB=True, maskB=L.B_UPPER)
@@ -267,6 +268,17 @@ def _sample_TG(st, zc):
     for d in range(D):
         PL = H.bmm(PG, st["lW"][d], maskB=L.B_LOWER)
         var_g[:, d] = var0 + (PL * PL).sum(2)
+    return T, mu_g, var_g, o_p, o_g, o_f
+
+
+def _sample_TG(st, zc):
+    """The part of a chunk that sample_Y, sample_FY and summarize_FY share: tilde-ell T (S, N) and the latent
+    G (S, D, N) drawn from the marginals of _sample_T_moments with the z_g of the noise block.  Also returns the
+    column offsets of z_p and z_f in zc."""
+    N, D = st["N"], st["D"]
+    S = zc.shape[0]
+    T, mu_g, var_g, o_p, o_g, o_f = _sample_T_moments(st, zc)
+    z_g = zc[:, o_g:o_g + D * N].reshape(S, D, N)
     G = mu_g.transpose(1, 2) + torch.sqrt(var_g + JIT) * z_g           # (S, D, N)
     return T, G, o_p, o_f
 
@@ -740,4 +752,159 @@ def summarize_Y(model, X_list, Y_list=None, n_sample=1000, index=None, quantiles
             out["coverage"] = torch.stack([mean_of(inside[p], ok[p]) for p in parts])
     if keep_samples:
         out["Ys"], out["Fs"], out["tilde_ells"] = Ys, Fs, Ts
+    return out
+
+
+def observed_grid(X_list, Y_list, x):
+    """The bridge from the reference's per-output lists to the grid that impute_Y conditions on: Y_obs (N, D)
+    float64 numpy, entry (n, d) the y of output d where X_list[d] contains x[n] exactly (the first hit wins), else
+    NaN.  Host logic; X_list[d] need not be sorted and may hold duplicates."""
+    if len(X_list) != len(Y_list):
+        raise ValueError("Y_list must match X_list entry by entry")
+    x = np.asarray(x, np.float64).reshape(-1)
+    out = np.full((x.shape[0], len(X_list)), np.nan)
+    for d, (xd, yd) in enumerate(zip(X_list, Y_list)):
+        xd, yd = np.asarray(xd, np.float64).reshape(-1), np.asarray(yd, np.float64).reshape(-1)
+        if xd.shape != yd.shape:
+            raise ValueError("Y_list must match X_list entry by entry")
+        if xd.size == 0:
+            continue
+        order = np.argsort(xd, kind="stable")                            # stable: the first of equal inputs first
+        xs = xd[order]
+        pos = np.minimum(np.searchsorted(xs, x, side="left"), xs.size - 1)
+        hit = xs[pos] == x
+        out[hit, d] = yd[order[pos[hit]]]
+    return out
+
+
+def _impute_args(D, Y_obs, Y_true, n_sample, quantiles, N=None):
+    """Validation of impute_Y that needs no device -> (Y_obs, Y_true as float64 numpy, n_sample, quantiles)."""
+    qs = [float(q) for q in quantiles]
+    if any(not 0.0 <= q <= 1.0 for q in qs):
+        raise ValueError("quantiles must lie in [0, 1]")
+    n_sample = int(n_sample)
+    if n_sample < 1:
+        raise ValueError("n_sample must be at least 1")
+    Y_obs = np.asarray(Y_obs.detach().cpu() if torch.is_tensor(Y_obs) else Y_obs, np.float64)
+    if Y_obs.ndim != 2 or Y_obs.shape[1] != D or (N is not None and Y_obs.shape[0] != N):
+        raise ValueError(f"Y_obs must be (N, D) = ({'N' if N is None else N}, {D}), got {Y_obs.shape}")
+    if Y_true is not None:
+        Y_true = np.asarray(Y_true.detach().cpu() if torch.is_tensor(Y_true) else Y_true, np.float64)
+        if Y_true.shape != Y_obs.shape:
+            raise ValueError(f"Y_true must have the shape of Y_obs {Y_obs.shape}, got {Y_true.shape}")
+    return Y_obs, Y_true, n_sample, qs
+
+
+def impute_Y(model, x, Y_obs, Y_true=None, n_sample=1000, quantiles=(0.025, 0.975), noise_tape=None,
+             keep_samples=False):
+    """Predict the missing outputs at the inputs x (N,) from the outputs observed at the SAME inputs: Y_obs (N, D)
+    holds the observations, NaN where an output is missing (observed_grid builds it from per-output lists).  This
+    is what makes the model collaborative at prediction time: the outputs share the latent g through L(x), so an
+    output observed at x_n informs the others there.  Per posterior sample s (tilde_ell, L and the MGP_d marginals
+    mu_g, var_g of the latent, drawn exactly as sample_FY draws them: same setup, chunking, noise layout
+    [z_v M][z_t N][z_p Q N][z_g D N][z_f N D] and stream, so the same seed or tape gives the same tilde_ell and L
+    samples) the latent G is integrated out, y(x_n) ~ N(L mu_g, L V L^T + s2 I) with V = diag(var_g + 1e-4) and
+    s2 = sigma2_err + 1e-4 (z_g is consumed, not used), and every missing entry gets its conditional mean mu_s and
+    variance v_s given the row's observed entries.  The predictive of an entry is the equal-weight mixture of
+    N(mu_s, v_s) over the samples.  Each chunk is one fused launch (csrc/ycond.hip) that never stores an
+    (S, N, D, D) tensor.
+
+    Returns a dict of device tensors over the E missing entries in (n, d) row-major order: "missing" (E, 2) their
+    (n, d); "mean" and "sd" (mixture mean and population sd of y); "F_mean" and "F_sd" (noise-free: v_s - s2);
+    "Y_filled" (N, D), Y_obs with the means written into the gaps; "tilde_ell_mean" (N,); with non-empty quantiles
+    "quantiles" (len(quantiles), E), the sample quantiles of the draws mu_s + sqrt(v_s) z_f with z_f the entry's
+    noise of the sample_FY slot (one draw per sample, not the exact mixture quantile).  mu_s and v_s are collected
+    as (S, E) only when quantiles or keep_samples ask for them: 16 S E bytes, not batched.  keep_samples=True
+    adds "Mu", "Var" (S, E) and "tilde_ells" (S, N).
+
+    With Y_true (N, D) the missing entries whose truth is finite are scored: "lpd" (E,) the log of the mixture
+    density at the truth (NaN where not scored) and "mean_lpd"; "rmse" (D,) per output and "rmse_all", of "mean";
+    "coverage" (D,) of the outermost quantile band (needs two quantiles); "n_scored" (D,).
+
+    A row with no missing entry costs nothing; with no missing entry at all every result has E = 0.  An all-NaN
+    Y_obs conditions on nothing: the result is the unconditional predictive of sample_FY's Y, Rao-Blackwellised
+    over G and the observation noise.
+
+    What this is not: the conditioning is pointwise in x -- an observed output informs the others at the same
+    input only, not at neighbouring inputs.  And observations that were already in the training set are used
+    twice, once through the variational posterior and once here; the clean protocol holds the test inputs out of
+    training for every output."""
+    Y_obs, Y_true, n_sample, qs = _impute_args(model.D, Y_obs, Y_true, n_sample, quantiles)
+    dev = model.device_
+    x = torch.as_tensor(x).reshape(-1, 1).to(F64).to(dev).contiguous()
+    if Y_obs.shape[0] != x.shape[0]:
+        raise ValueError(f"Y_obs must be (N, D) = ({x.shape[0]}, {model.D}), got {Y_obs.shape}")
+    st = _sampling_setup(model, x)
+    N, D, M = st["N"], st["D"], st["M"]
+    Q = len(st["pairs"])
+    per = M + N + Q * N + D * N + N * D
+    draws = _Draws(dev, noise_tape)
+    s2 = st["s2_err"] + JIT
+    Yo = torch.from_numpy(np.ascontiguousarray(Y_obs)).to(dev)
+    e_off, missing = H.missing_table(Yo)
+    E = int(missing.shape[0])
+    flat = missing[:, 0] * D + missing[:, 1]
+    z = lambda *shape: torch.zeros(*shape, dtype=F64, device=dev)
+    mu_sum, y2_sum, f2_sum, T_sum = z(E), z(E), z(E), z(N)
+    collect = bool(qs) or keep_samples
+    Mu = Var = Yd = None
+    if collect:
+        Mu, Var = torch.empty(n_sample, E, dtype=F64, device=dev), torch.empty(n_sample, E, dtype=F64, device=dev)
+    if qs:
+        Yd = torch.empty(n_sample, E, dtype=F64, device=dev)
+    Ts = torch.empty(n_sample, N, dtype=F64, device=dev) if keep_samples else None
+    y = lse_max = lse_sum = None
+    if Y_true is not None:
+        y = torch.from_numpy(np.ascontiguousarray(Y_true)).to(dev).reshape(-1)[flat].contiguous()
+        lse_max, lse_sum = torch.full((E,), float("-inf"), dtype=F64, device=dev), z(E)
+    chunk = _chunk_size(n_sample, N, M)
+    ws = H.ycond_workspace(D, N, chunk, dev) if E > 0 else None
+    done = 0
+    while done < n_sample:
+        S = min(chunk, n_sample - done)
+        zc = draws.take(S, per)
+        T, mu_g, var_g, o_p, o_g, o_f = _sample_T_moments(st, zc)
+        T_sum += T.sum(0)
+        if Ts is not None:
+            Ts[done:done + S] = T
+        if E > 0:
+            H.ycond_accum_(st["pair_mu"], st["pair_sd"], zc[:, o_p:], mu_g.contiguous(),
+                           var_g.transpose(1, 2).contiguous(), Yo, s2, e_off, mu_sum, y2_sum, f2_sum, y_true=y,
+                           lse_max=lse_max, lse_sum=lse_sum, Mu=Mu, Var=Var, s_off=done, ws=ws)
+            if qs:
+                z_f = zc[:, o_f:].index_select(1, flat)
+                Yd[done:done + S] = Mu[done:done + S] + torch.sqrt(Var[done:done + S]) * z_f
+        done += S
+    mean = mu_sum / n_sample
+    filled = Yo.clone()
+    filled.reshape(-1)[flat] = mean
+    out = {"missing": missing, "mean": mean, "sd": _pop_sd(y2_sum / n_sample, mean),
+           "F_mean": mean.clone(), "F_sd": _pop_sd(f2_sum / n_sample, mean), "Y_filled": filled,
+           "tilde_ell_mean": T_sum / n_sample}
+    Yq = None
+    if qs:
+        Yq = _quantiles_dim0(Yd, qs)
+        out["quantiles"] = Yq
+    if y is not None:
+        ok = torch.isfinite(y)
+        nan = torch.full((), float("nan"), dtype=F64, device=dev)
+        lpd = torch.where(ok, lse_max + torch.log(lse_sum) - float(np.log(n_sample)), nan)
+        okf = ok.to(F64)
+        d_of = missing[:, 1]
+
+        def per_output(v):                                               # sum over the scored entries of each output
+            return z(D).index_add_(0, d_of, torch.where(ok, v, torch.zeros_like(v)))
+
+        n_sc = per_output(okf)                                           # 0 / 0 = NaN: none scored
+        err2 = (mean - y) ** 2
+        out["lpd"] = lpd
+        out["mean_lpd"] = torch.where(ok, lpd, torch.zeros_like(lpd)).sum() / okf.sum()
+        out["rmse"] = torch.sqrt(per_output(err2) / n_sc)
+        out["rmse_all"] = torch.sqrt(per_output(err2).sum() / okf.sum())
+        out["n_scored"] = n_sc.to(torch.long)
+        if len(qs) >= 2:
+            lo, hi = Yq[int(np.argmin(qs))], Yq[int(np.argmax(qs))]
+            out["coverage"] = per_output(((y >= lo) & (y <= hi)).to(F64)) / n_sc
+    if keep_samples:
+        out["Mu"], out["Var"], out["tilde_ells"] = Mu, Var, Ts
     return out

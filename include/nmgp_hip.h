@@ -813,6 +813,41 @@ int nmgp_pcorr_accum_groups_f64(const double* pair_mu, const double* pair_sd, in
                                 const int32_t* goff, const int32_t* gent, int K, int E, double* Cg, int64_t ld_cg,
                                 int64_t sg_off, void* ws, int64_t ws_bytes, hipStream_t stream);
 
+/* Conditional prediction of the missing outputs at an input from the outputs observed at the same input, per
+ * posterior sample, fused (csrc/ycond.hip).  The reference has no such code; the quantity is a function of what
+ * NMGP.sample_FY samples (code/nmgp_dsvi.py:519-569).  fp64.  For every sample s < S and input n < N, with L built
+ * from the pair samples exactly as in nmgp_pcorr_accum_f64, mu_g / var_g (S, N, D) contiguous the marginals of the
+ * latent G of that sample, V = diag(var_g + 1e-4) and s2 the noise variance (jitter included):
+ *   y(x_n) ~ N(L mu_g, L V L^T + s2 I).  Row n of Y_obs (N, D contiguous) has observed (finite) and missing
+ *   (non-finite) entries;  A = V^-1 + L^T diag(w) L with w_o = 1 / s2 where observed and 0 elsewhere,
+ *   b = V^-1 mu_g + L^T (w o y),  A = R R^T (tiled Cholesky on v_mfma_f64_16x16x4_f64),  c = R^-1 b,
+ *   w_h = R^-1 l_h (l_h = row h of L as a column),  mu = w_h^T c,  v = |w_h|^2 + s2  for every missing h.
+ * The missing entries of Y_obs in (n, d) row-major order are the E entries; e_off (N + 1 device int32) is the
+ * prefix sum of the rows' missing counts (e_off[0] = 0, e_off[N] = E) and must agree with the mask of Y_obs: a
+ * table that does not cannot make the kernel leave its buffers (its offsets are clamped to 0..E and made monotone,
+ * a row's count is clipped to the mask's), but the entries it misplaces are undefined.  A row without a missing entry does no work.
+ *   mu_sum[e] += mu,  y2_sum[e] += v + mu^2,  f2_sum[e] += v - s2 + mu^2   (ACCUMULATED: the caller zeroes them);
+ *   with y_true (E, NULL = none): (lse_max[e], lse_sum[e]) <- the running log-sum-exp state of
+ *   log N(y_true[e] | mu, v) over the samples, combined as in nmgp_y_accum_f64 (the caller starts it at (-inf, 0));
+ *   a non-finite y_true[e] leaves its state untouched;
+ *   with Mu / Var (both or neither; ld rows of E): Mu[(s_off + s) * E + e] = mu, Var[...] = v, every addressed
+ *   element written once, the other rows left alone.
+ * A sample whose L_kk is 0, inf or NaN at input n, or whose var_g + 1e-4 is not finite and positive there, gives
+ * NaN mu and v at every entry of that input (and NaN sums); other inputs are not affected.  Slicing, workspace
+ * (nmgp_ycond_workspace_size bytes, 0 when unsliced) and determinism as nmgp_pcorr_accum_f64: no floating-point
+ * atomics, the same call gives the same bits.  L and A share one workgroup's LDS (149.5 KiB at D = 128).  Returns
+ * 0 (nothing launched when S, N or E is 0), NMGP_ERR_YCOND_ARG before any launch when D is outside 1..128, a
+ * count or s_off is negative, E > N D, s2 is not positive, ld_pair < N, z_stride < 0, an input or a sum is NULL,
+ * exactly one of Mu / Var is NULL or ld < s_off + S, y_true is given without lse_max / lse_sum, or the workspace is
+ * missing / too small.                                                                                          */
+#define NMGP_ERR_YCOND_ARG (-65)
+int64_t nmgp_ycond_workspace_size(int D, int N, int S);
+int nmgp_ycond_accum_f64(const double* pair_mu, const double* pair_sd, int64_t ld_pair, const double* z_p,
+                         int64_t z_stride, const double* mu_g, const double* var_g, const double* Y_obs, double s2,
+                         int D, int N, int S, const int32_t* e_off, int E, double* mu_sum, double* y2_sum,
+                         double* f2_sum, const double* y_true, double* lse_max, double* lse_sum, double* Mu,
+                         double* Var, int64_t ld, int64_t s_off, void* ws, int64_t ws_bytes, hipStream_t stream);
+
 /* Whole-step HIP graphs (the reference runs its step eagerly, code/nmgp_dsvi.py:829-854; the build captures
  * noise -> forward -> backward -> Adam once and replays it).  Capture goes straight through the HIP runtime:
  * begin on `stream` (thread-local mode; other streams join through event waits and must join back before
