@@ -5,13 +5,16 @@
 // the credible band of a group mean.  The (S, N, D, D) tensor is never stored, and neither are per-pair samples: the
 // reduction over the pairs happens next to the correlation matrix, in LDS.
 //
-// One workgroup (4 waves) per (input n, slice of samples), the tile layout of fy_tiles.hpp and the XCD-aware input
-// mapping of fy.hip.  LDS: L (T tiles), the normalised lower triangle R (T tiles) and Is -- 2 x 72 KiB + 1 KiB = 145
+// One workgroup (4 waves) per (input n, slice of samples), the tile layout and the XCD-aware input mapping of
+// fy_tiles.hpp.  LDS: L (T tiles), the normalised lower triangle R (T tiles) and Is -- 2 x 72 KiB + 1 KiB = 145
 // KiB at D = 128, 2 x 20 KiB + 0.5 KiB at D = 50: the budget of pcorr.hip, under the CU's 160 KiB at every D <= 128.
-// Per sample: pair samples -> L; diagonal of cov -> Is (the two-threads-per-row sum of fy.hip, the same bits); cov
-// tiles on v_mfma_f64_16x16x4_f64 in the tile dealing and k order of fy.hip, normalised in its order (acc * isi *
-// isj, diagonal 1 where finite, non-finite values kept), written to R instead of being accumulated; then the group
-// reduction of fy_groups.hpp.  So a group of one pair is bit for bit the correlation that fy.hip accumulates.
+// Per sample the stages that fy.hip runs: pair samples -> L and diagonal of cov -> Is from the same definitions
+// (fy_load_L, fy_row_sums of fy_tiles.hpp); cov tiles on v_mfma_f64_16x16x4_f64 in the tile dealing and k order of
+// fy.hip, normalised in its order (acc * isi * isj, diagonal 1 where finite, non-finite values kept), written to R
+// instead of being accumulated -- a copy of fy.hip's loop, not a shared function: handing the element to a sink
+// cost 1 % at D = 50 with the 28-group table (tools/corr_group_probe.py); then the group reduction of
+// fy_groups.hpp.  So a group of one pair is bit for bit the correlation that fy.hip accumulates, which
+// tests/test_gpu_corr_groups.py checks.
 //
 // Nothing is accumulated across samples: no workspace, no atomics, every (k, n, s) is written once by the one
 // workgroup that owns (n, s), from that sample alone; the slices (fy_slicing) only fill the chip when N < 256.
@@ -43,8 +46,7 @@ __global__ __launch_bounds__(kFyThreads) void corr_group_kernel(
   double* Is = Rt + T * kFyTileElems;                   // NT * 16: sqrt(1 / cov_ii), 0 past D
   __shared__ double part[2 * kFyWaves];                 // wave sums of a group that the whole workgroup adds
 
-  const int bid = blockIdx.x;
-  const int n = (bid % kFyXcds) * (n_blocks / kFyXcds) + bid / kFyXcds;   // as fy.hip: neighbours share an XCD
+  const int n = fy_block_input(n_blocks);
   if (n >= N) return;
   const int slice = blockIdx.y;
   const int s0 = slice * per, s1 = min(S, s0 + per);
@@ -53,37 +55,20 @@ __global__ __launch_bounds__(kFyThreads) void corr_group_kernel(
 
   for (int e = tid; e < 2 * T * kFyTileElems + NT * kFyTile; e += kFyThreads) cg_smem[e] = 0.0;
 
-  const int ar = lane & 15, ak = lane >> 4;             // MFMA operand row / k of this lane
-  const int frow = tid >> 1, fhalf = tid & 1;           // two threads per row of L, columns of one parity each
+  const int ar = lane & 15, ak = lane >> 4;
   const int64_t k_stride = (int64_t)N * ld_c;
   int par = 0;
   __syncthreads();
 
   for (int s = s0; s < s1; ++s) {
     // ---- pair samples -> L tiles
-    const double* zp = z_p + (int64_t)s * z_stride + n;
-#pragma unroll 1
-    for (int q = tid; q < Q; q += kFyThreads) {
-      const int i = fy_tri_row(q);
-      const int j = q - i * (i + 1) / 2;
-      const double l = pair_mu[(int64_t)q * ld_pair + n] + pair_sd[(int64_t)q * ld_pair + n] * zp[(int64_t)q * N];
-      Lt[(fy_ntiles(i >> 4) + (j >> 4)) * kFyTileElems + fy_tile_off(i & 15, j & 15)] = i == j ? exp(l) : l;
-    }
+    fy_load_L<false>(Lt, pair_mu, pair_sd, ld_pair, z_p + (int64_t)s * z_stride + n, n, N, Q, tid, nullptr);
     __syncthreads();
 
     // ---- the diagonal of cov
     {
-      double c = 0.0;
-      if (frow < D) {
-        const int ti = frow >> 4, r = frow & 15;
-        const double* rowt = Lt + fy_ntiles(ti) * kFyTileElems;
-        for (int j = fhalf; j <= frow; j += 2) {
-          const double v = rowt[(j >> 4) * kFyTileElems + fy_tile_off(r, j & 15)];
-          c = fma(v, v, c);
-        }
-      }
-      c += __shfl_xor(c, 1, 64);
-      if (frow < D && fhalf == 0) Is[frow] = sqrt(1.0 / c);
+      const double c = fy_row_sums<false>(Lt, nullptr, D, tid, nullptr);
+      if ((tid >> 1) < D && (tid & 1) == 0) Is[tid >> 1] = sqrt(1.0 / c);
     }
     __syncthreads();
 
@@ -127,25 +112,6 @@ __global__ __launch_bounds__(kFyThreads) void corr_group_kernel(
   }
 }
 
-template <int NT>
-static int cgroup_launch(const double* pair_mu, const double* pair_sd, int64_t ld_pair, const double* z_p,
-                         int64_t z_stride, int D, int N, int S, int nsl, int per, const int32_t* goff,
-                         const uint32_t* gent, int K, int E, double* C, int64_t ld_c, int64_t s_off, hipStream_t s) {
-  const size_t smem = (size_t)(2 * fy_ntiles(NT) * kFyTileElems + NT * kFyTile) * sizeof(double);
-  static bool attr_done = false;
-  if (!attr_done) {
-    (void)hipFuncSetAttribute((const void*)corr_group_kernel<NT>, hipFuncAttributeMaxDynamicSharedMemorySize,
-                              (int)smem);
-    attr_done = true;
-  }
-  const int n_blocks = (N + kFyXcds - 1) / kFyXcds * kFyXcds;
-  hipLaunchKernelGGL(corr_group_kernel<NT>, dim3((unsigned)n_blocks, (unsigned)nsl), dim3(kFyThreads), smem, s,
-                     pair_mu, pair_sd, ld_pair, z_p, z_stride, D, N, S, per, goff, gent, K, E, C, ld_c, s_off,
-                     n_blocks);
-  NMGP_CHECK_LAUNCH();
-  return NMGP_OK;
-}
-
 }  // namespace nmgp
 
 using namespace nmgp;
@@ -162,24 +128,12 @@ int nmgp_corr_group_f64(const double* pair_mu, const double* pair_sd, int64_t ld
     return NMGP_ERR_CGROUP_ARG;
   int nsl, per;
   fy_slicing(N, S, &nsl, &per);
-  const int nt = (D + kFyTile - 1) / kFyTile;
-#define NMGP_CGROUP_CASE(NT_)                                                                                     \
-  case NT_:                                                                                                       \
-    return cgroup_launch<NT_>(pair_mu, pair_sd, ld_pair, z_p, z_stride, D, N, S, nsl, per, goff,                 \
-                              (const uint32_t*)gent, K, E, C, ld_c, s_off, stream);
-  switch (nt) {
-    NMGP_CGROUP_CASE(1)
-    NMGP_CGROUP_CASE(2)
-    NMGP_CGROUP_CASE(3)
-    NMGP_CGROUP_CASE(4)
-    NMGP_CGROUP_CASE(5)
-    NMGP_CGROUP_CASE(6)
-    NMGP_CGROUP_CASE(7)
-    NMGP_CGROUP_CASE(8)
-    default:
-      return NMGP_ERR_CGROUP_ARG;
-  }
-#undef NMGP_CGROUP_CASE
+  return fy_dispatch_nt((D + kFyTile - 1) / kFyTile, NMGP_ERR_CGROUP_ARG, [&](auto nt) {
+    constexpr int NT = decltype(nt)::value;
+    const size_t smem = (size_t)(2 * fy_ntiles(NT) * kFyTileElems + NT * kFyTile) * sizeof(double);
+    return fy_launch<corr_group_kernel<NT>>(smem, N, nsl, stream, pair_mu, pair_sd, ld_pair, z_p, z_stride, D, N, S,
+                                            per, goff, (const uint32_t*)gent, K, E, C, ld_c, s_off);
+  });
 }
 
 }  // extern "C"

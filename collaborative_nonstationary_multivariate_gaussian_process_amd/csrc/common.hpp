@@ -14,6 +14,9 @@ namespace nmgp {
 
 constexpr int kWave = 64;
 
+// The caller's workspace (ws, ws_bytes) holds the `need` bytes that an entry point's size function asks for.
+inline bool ws_covers(int64_t need, const void* ws, int64_t ws_bytes) { return need <= 0 || (ws && ws_bytes >= need); }
+
 // Global-address-space pointer.  Pointers that arrive inside descriptor structs are generic, and
 // generic (flat) loads count against lgkmcnt as well as vmcnt: an LDS wait would then also wait
 // for every outstanding prefetch.  Casting to addrspace(1) gives global_load/store instead.

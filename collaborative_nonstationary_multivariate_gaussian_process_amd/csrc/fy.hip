@@ -28,10 +28,7 @@ __global__ __launch_bounds__(kFyThreads) void fy_accum_kernel(
   double* Gs = Lt + T * kFyTileElems;                   // NT * 16
   double* Is = Gs + NT * kFyTile;                       // NT * 16: sqrt(1 / cov_ii), 0 past D
 
-  // consecutive inputs share an XCD (and its L2): the (Q, N) operands are read at one n per workgroup, so the 8
-  // inputs of a 64-byte line are best fetched by workgroups behind one L2
-  const int bid = blockIdx.x;
-  const int n = (bid % kFyXcds) * (n_blocks / kFyXcds) + bid / kFyXcds;
+  const int n = fy_block_input(n_blocks);
   if (n >= N) return;
   const int slice = blockIdx.y;
   const int s0 = slice * per, s1 = min(S, s0 + per);
@@ -43,41 +40,21 @@ __global__ __launch_bounds__(kFyThreads) void fy_accum_kernel(
   f64x4 sum[KMAX], sq[KMAX];
 #pragma unroll
   for (int k = 0; k < KMAX; ++k) sum[k] = sq[k] = f64x4{0.0, 0.0, 0.0, 0.0};
-
   const int ar = lane & 15, ak = lane >> 4;             // MFMA operand row / k of this lane
-  const int frow = tid >> 1, fhalf = tid & 1;           // Y: two threads per row of L, columns of one parity each
   __syncthreads();
 
   for (int s = s0; s < s1; ++s) {
     // ---- pair samples -> L tiles; G column -> LDS
-    const double* zp = z_p + (int64_t)s * z_stride + n;
-    // not unrolled: with 4 or 8 pairs' loads in flight per lane the launch took 20-25 % longer at D = 50 and 128
-    // (each lane's load is a 64-byte line of its own, shared only with the neighbouring inputs' workgroups)
-#pragma unroll 1
-    for (int q = tid; q < Q; q += kFyThreads) {
-      const int i = fy_tri_row(q);
-      const int j = q - i * (i + 1) / 2;
-      const double l = pair_mu[(int64_t)q * ld_pair + n] + pair_sd[(int64_t)q * ld_pair + n] * zp[(int64_t)q * N];
-      Lt[(fy_ntiles(i >> 4) + (j >> 4)) * kFyTileElems + fy_tile_off(i & 15, j & 15)] = i == j ? exp(l) : l;
-    }
+    fy_load_L<false>(Lt, pair_mu, pair_sd, ld_pair, z_p + (int64_t)s * z_stride + n, n, N, Q, tid, nullptr);
     if (tid < D) Gs[tid] = G[((int64_t)s * D + tid) * N + n];
     __syncthreads();
 
     // ---- Y row and the diagonal of cov
     {
-      double f = 0.0, c = 0.0;
-      if (frow < D) {
-        const int ti = frow >> 4, r = frow & 15;
-        const double* rowt = Lt + fy_ntiles(ti) * kFyTileElems;
-        for (int j = fhalf; j <= frow; j += 2) {
-          const double v = rowt[(j >> 4) * kFyTileElems + fy_tile_off(r, j & 15)];
-          f = fma(v, Gs[j], f);
-          c = fma(v, v, c);
-        }
-      }
-      f += __shfl_xor(f, 1, 64);
-      c += __shfl_xor(c, 1, 64);
-      if (frow < D && fhalf == 0) {
+      const int frow = tid >> 1;
+      double f;
+      const double c = fy_row_sums<true>(Lt, Gs, D, tid, &f);
+      if (frow < D && (tid & 1) == 0) {
         const int64_t o = ((int64_t)s * N + n) * D + frow;
         Y[o] = f + sd_err * z_f[(int64_t)s * z_stride + (int64_t)n * D + frow];
         Is[frow] = sqrt(1.0 / c);
@@ -159,11 +136,11 @@ __global__ __launch_bounds__(kFyThreads) void fy_accum_kernel(
   }
 }
 
-// corr_sum / corr_sq += the slices' partial sums, in slice order; one thread per (n, i, j), the partials hold
-// the lower triangle only.
-__global__ __launch_bounds__(256) void fy_reduce_kernel(const double* __restrict__ ws, int nsl, int D, int N,
-                                                         double* __restrict__ corr_sum,
-                                                         double* __restrict__ corr_sq) {
+// out_sum / out_sq += the slices' partial sums, in slice order; one thread per (n, i, j), the partials hold the
+// lower triangle only.
+__global__ __launch_bounds__(256) void fy_tri_reduce_kernel(const double* __restrict__ ws, int nsl, int D, int N,
+                                                             double* __restrict__ out_sum,
+                                                             double* __restrict__ out_sq) {
   const int64_t dd = (int64_t)D * D;
   const int64_t e = (int64_t)blockIdx.x * 256 + threadIdx.x;
   if (e >= (int64_t)N * dd) return;
@@ -176,25 +153,14 @@ __global__ __launch_bounds__(256) void fy_reduce_kernel(const double* __restrict
     a += p[0];
     b += p[dd];
   }
-  corr_sum[e] += a;
-  corr_sq[e] += b;
+  out_sum[e] += a;
+  out_sq[e] += b;
 }
 
-template <int NT>
-static int fy_launch(const double* pair_mu, const double* pair_sd, int64_t ld_pair, const double* G,
-                     const double* z_p, const double* z_f, int64_t z_stride, double sd_err, int D, int N, int S,
-                     int nsl, int per, double* Y, double* corr_sum, double* corr_sq, double* ws, hipStream_t s) {
-  const size_t smem = (size_t)(fy_ntiles(NT) * kFyTileElems + 2 * NT * kFyTile) * sizeof(double);
-  static bool attr_done = false;
-  if (!attr_done) {
-    (void)hipFuncSetAttribute((const void*)fy_accum_kernel<NT>, hipFuncAttributeMaxDynamicSharedMemorySize,
-                              (int)smem);
-    attr_done = true;
-  }
-  const int n_blocks = (N + kFyXcds - 1) / kFyXcds * kFyXcds;
-  hipLaunchKernelGGL(fy_accum_kernel<NT>, dim3((unsigned)n_blocks, (unsigned)nsl), dim3(kFyThreads), smem, s,
-                     pair_mu, pair_sd, ld_pair, G, z_p, z_f, z_stride, sd_err, D, N, S, per, Y, corr_sum, corr_sq, ws,
-                     n_blocks);
+int fy_tri_reduce(const double* ws, int nsl, int D, int N, double* out_sum, double* out_sq, hipStream_t stream) {
+  const int64_t total = (int64_t)N * D * D;
+  hipLaunchKernelGGL(fy_tri_reduce_kernel, dim3((unsigned)((total + 255) / 256)), dim3(256), 0, stream, ws, nsl, D, N,
+                     out_sum, out_sq);
   NMGP_CHECK_LAUNCH();
   return NMGP_OK;
 }
@@ -205,12 +171,7 @@ using namespace nmgp;
 
 extern "C" {
 
-int64_t nmgp_fy_workspace_size(int D, int N, int S) {
-  if (D < 1 || D > kFyMaxD || N <= 0 || S <= 0) return 0;
-  int nsl, per;
-  fy_slicing(N, S, &nsl, &per);
-  return nsl == 1 ? 0 : (int64_t)nsl * N * 2 * D * D * (int64_t)sizeof(double);
-}
+int64_t nmgp_fy_workspace_size(int D, int N, int S) { return fy_tri_workspace_bytes(D, N, S); }
 
 int nmgp_fy_accum_f64(const double* pair_mu, const double* pair_sd, int64_t ld_pair, const double* G,
                       const double* z_p, const double* z_f, int64_t z_stride, double sd_err, int D, int N, int S,
@@ -221,36 +182,15 @@ int nmgp_fy_accum_f64(const double* pair_mu, const double* pair_sd, int64_t ld_p
   if (ld_pair < N || z_stride < 0 || N > 0x7fffffff - kFyXcds) return NMGP_ERR_FY_ARG;
   int nsl, per;
   fy_slicing(N, S, &nsl, &per);
-  const int64_t need = nmgp_fy_workspace_size(D, N, S);
-  if (need > 0 && (!ws || ws_bytes < need)) return NMGP_ERR_FY_ARG;
-  const int nt = (D + kFyTile - 1) / kFyTile;
-  int rc;
-#define NMGP_FY_CASE(NT_)                                                                                          \
-  case NT_:                                                                                                        \
-    rc = fy_launch<NT_>(pair_mu, pair_sd, ld_pair, G, z_p, z_f, z_stride, sd_err, D, N, S, nsl, per, Y, corr_sum, \
-                        corr_sq, (double*)ws, stream);                                                             \
-    break;
-  switch (nt) {
-    NMGP_FY_CASE(1)
-    NMGP_FY_CASE(2)
-    NMGP_FY_CASE(3)
-    NMGP_FY_CASE(4)
-    NMGP_FY_CASE(5)
-    NMGP_FY_CASE(6)
-    NMGP_FY_CASE(7)
-    NMGP_FY_CASE(8)
-    default:
-      return NMGP_ERR_FY_ARG;
-  }
-#undef NMGP_FY_CASE
-  if (rc != NMGP_OK) return rc;
-  if (nsl > 1) {
-    const int64_t total = (int64_t)N * D * D;
-    hipLaunchKernelGGL(fy_reduce_kernel, dim3((unsigned)((total + 255) / 256)), dim3(256), 0, stream,
-                       (const double*)ws, nsl, D, N, corr_sum, corr_sq);
-    NMGP_CHECK_LAUNCH();
-  }
-  return NMGP_OK;
+  if (!ws_covers(fy_tri_workspace_bytes(D, N, S), ws, ws_bytes)) return NMGP_ERR_FY_ARG;
+  const int rc = fy_dispatch_nt((D + kFyTile - 1) / kFyTile, NMGP_ERR_FY_ARG, [&](auto nt) {
+    constexpr int NT = decltype(nt)::value;
+    const size_t smem = (size_t)(fy_ntiles(NT) * kFyTileElems + 2 * NT * kFyTile) * sizeof(double);
+    return fy_launch<fy_accum_kernel<NT>>(smem, N, nsl, stream, pair_mu, pair_sd, ld_pair, G, z_p, z_f, z_stride,
+                                          sd_err, D, N, S, per, Y, corr_sum, corr_sq, (double*)ws);
+  });
+  if (rc != NMGP_OK || nsl == 1) return rc;
+  return fy_tri_reduce((const double*)ws, nsl, D, N, corr_sum, corr_sq, stream);
 }
 
 }  // extern "C"

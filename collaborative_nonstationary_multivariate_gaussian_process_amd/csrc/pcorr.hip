@@ -4,8 +4,8 @@
 // The (S, N, D, D) tensor is never stored.  The reference has no partial-correlation code; the quantity is a pure
 // function of the covariance of NMGP.sample_FY (reference code/nmgp_dsvi.py:567-569).
 //
-// One workgroup (4 waves) per (input n, slice of samples), L and W side by side in LDS in the tile layout of fy.hip
-// (fy_tiles.hpp; 2 x 72 KiB at D = 128, 2 x 20 KiB at D = 50, plus 1 KiB: under the CU's 160 KiB at every D <= 128).
+// One workgroup (4 waves) per (input n, slice of samples), L and W side by side in LDS in the tile layout of
+// fy_tiles.hpp (2 x 72 KiB at D = 128, 2 x 20 KiB at D = 50, plus 1 KiB: under the CU's 160 KiB at every D <= 128).
 // The rows of L past D carry a unit diagonal, so W is [[W_D, 0], [0, I]] and Omega's leading block is untouched.
 //
 // The inverse: the 16 x 16 diagonal tiles are inverted by forward substitution, one tile per 16 lanes (lane = column
@@ -53,8 +53,7 @@ __global__ __launch_bounds__(kFyThreads) void pcorr_accum_kernel(
   __shared__ int bad_flag[2];                           // a diagonal of L that is 0, inf or NaN, by sample parity
   __shared__ double part[2 * kFyWaves];                 // wave sums of a group that the whole workgroup adds
 
-  const int bid = blockIdx.x;
-  const int n = (bid % kFyXcds) * (n_blocks / kFyXcds) + bid / kFyXcds;   // as fy.hip: neighbours share an XCD
+  const int n = fy_block_input(n_blocks);
   if (n >= N) return;
   const int slice = blockIdx.y;
   const int s0 = slice * per, s1 = min(S, s0 + per);
@@ -80,7 +79,9 @@ __global__ __launch_bounds__(kFyThreads) void pcorr_accum_kernel(
   __syncthreads();
 
   for (int s = s0; s < s1; ++s) {
-    // ---- pair samples -> L tiles
+    // ---- pair samples -> L tiles: fy_load_L<true> of fy_tiles.hpp (which says why the loop is not unrolled),
+    // kept as a copy here, like the column sums and the exit of the sums below: with the shared functions the
+    // sums-only launch measured 2-3 % slower (tools/pcorr_probe.py), with every stage local as before
     const double* zp = z_p + (int64_t)s * z_stride + n;
 #pragma unroll 1
     for (int q = tid; q < Q; q += kFyThreads) {
@@ -249,59 +250,13 @@ __global__ __launch_bounds__(kFyThreads) void pcorr_accum_kernel(
   }
 }
 
-// pc_sum / pc_sq += the slices' partial sums, in slice order; one thread per (n, i, j), the partials hold the
-// lower triangle only.
-__global__ __launch_bounds__(256) void pcorr_reduce_kernel(const double* __restrict__ ws, int nsl, int D, int N,
-                                                            double* __restrict__ pc_sum, double* __restrict__ pc_sq) {
-  const int64_t dd = (int64_t)D * D;
-  const int64_t e = (int64_t)blockIdx.x * 256 + threadIdx.x;
-  if (e >= (int64_t)N * dd) return;
-  const int64_t n = e / dd;
-  const int ij = (int)(e - n * dd), i = ij / D, j = ij - i * D;
-  const int64_t src = (int64_t)max(i, j) * D + min(i, j);
-  double a = 0.0, b = 0.0;
-  for (int sl = 0; sl < nsl; ++sl) {
-    const double* p = ws + (((int64_t)sl * N + n) * 2) * dd + src;
-    a += p[0];
-    b += p[dd];
-  }
-  pc_sum[e] += a;
-  pc_sq[e] += b;
-}
-
-template <int NT>
-static int pcorr_launch(const double* pair_mu, const double* pair_sd, int64_t ld_pair, const double* z_p,
-                        int64_t z_stride, int D, int N, int S, int nsl, int per, double* pc_sum, double* pc_sq,
-                        const int32_t* pi, const int32_t* pj, int P, double* C, int64_t ld_c, int64_t s_off,
-                        const int32_t* goff, const uint32_t* gent, int K, int E, double* Cg, int64_t ld_cg,
-                        int64_t sg_off, double* ws, hipStream_t s) {
-  const size_t smem = (size_t)(2 * fy_ntiles(NT) * kFyTileElems + NT * kFyTile) * sizeof(double);
-  static bool attr_done = false;
-  if (!attr_done) {
-    (void)hipFuncSetAttribute((const void*)pcorr_accum_kernel<NT>, hipFuncAttributeMaxDynamicSharedMemorySize,
-                              (int)smem);
-    attr_done = true;
-  }
-  const int n_blocks = (N + kFyXcds - 1) / kFyXcds * kFyXcds;
-  hipLaunchKernelGGL(pcorr_accum_kernel<NT>, dim3((unsigned)n_blocks, (unsigned)nsl), dim3(kFyThreads), smem, s,
-                     pair_mu, pair_sd, ld_pair, z_p, z_stride, D, N, S, per, pc_sum, pc_sq, pi, pj, P, C, ld_c, s_off,
-                     goff, gent, K, E, Cg, ld_cg, sg_off, ws, n_blocks);
-  NMGP_CHECK_LAUNCH();
-  return NMGP_OK;
-}
-
 }  // namespace nmgp
 
 using namespace nmgp;
 
 extern "C" {
 
-int64_t nmgp_pcorr_workspace_size(int D, int N, int S) {
-  if (D < 1 || D > kFyMaxD || N <= 0 || S <= 0) return 0;
-  int nsl, per;
-  fy_slicing(N, S, &nsl, &per);
-  return nsl == 1 ? 0 : (int64_t)nsl * N * 2 * D * D * (int64_t)sizeof(double);
-}
+int64_t nmgp_pcorr_workspace_size(int D, int N, int S) { return fy_tri_workspace_bytes(D, N, S); }
 
 int nmgp_pcorr_accum_groups_f64(const double* pair_mu, const double* pair_sd, int64_t ld_pair, const double* z_p,
                                 int64_t z_stride, int D, int N, int S, double* pc_sum, double* pc_sq,
@@ -319,37 +274,16 @@ int nmgp_pcorr_accum_groups_f64(const double* pair_mu, const double* pair_sd, in
   if (K > 0 && (!goff || !gent || !Cg || E < K || ld_cg < sg_off + S)) return NMGP_ERR_PCORR_ARG;
   int nsl, per;
   fy_slicing(N, S, &nsl, &per);
-  const int64_t need = pc_sum ? nmgp_pcorr_workspace_size(D, N, S) : 0;
-  if (need > 0 && (!ws || ws_bytes < need)) return NMGP_ERR_PCORR_ARG;
-  const int nt = (D + kFyTile - 1) / kFyTile;
-  int rc;
-#define NMGP_PCORR_CASE(NT_)                                                                                       \
-  case NT_:                                                                                                        \
-    rc = pcorr_launch<NT_>(pair_mu, pair_sd, ld_pair, z_p, z_stride, D, N, S, nsl, per, pc_sum, pc_sq, pi, pj, P, \
-                           C, ld_c, s_off, goff, (const uint32_t*)gent, K, E, Cg, ld_cg, sg_off, (double*)ws,     \
-                           stream);                                                                                \
-    break;
-  switch (nt) {
-    NMGP_PCORR_CASE(1)
-    NMGP_PCORR_CASE(2)
-    NMGP_PCORR_CASE(3)
-    NMGP_PCORR_CASE(4)
-    NMGP_PCORR_CASE(5)
-    NMGP_PCORR_CASE(6)
-    NMGP_PCORR_CASE(7)
-    NMGP_PCORR_CASE(8)
-    default:
-      return NMGP_ERR_PCORR_ARG;
-  }
-#undef NMGP_PCORR_CASE
-  if (rc != NMGP_OK) return rc;
-  if (pc_sum && nsl > 1) {
-    const int64_t total = (int64_t)N * D * D;
-    hipLaunchKernelGGL(pcorr_reduce_kernel, dim3((unsigned)((total + 255) / 256)), dim3(256), 0, stream,
-                       (const double*)ws, nsl, D, N, pc_sum, pc_sq);
-    NMGP_CHECK_LAUNCH();
-  }
-  return NMGP_OK;
+  if (pc_sum && !ws_covers(fy_tri_workspace_bytes(D, N, S), ws, ws_bytes)) return NMGP_ERR_PCORR_ARG;
+  const int rc = fy_dispatch_nt((D + kFyTile - 1) / kFyTile, NMGP_ERR_PCORR_ARG, [&](auto nt) {
+    constexpr int NT = decltype(nt)::value;
+    const size_t smem = (size_t)(2 * fy_ntiles(NT) * kFyTileElems + NT * kFyTile) * sizeof(double);
+    return fy_launch<pcorr_accum_kernel<NT>>(smem, N, nsl, stream, pair_mu, pair_sd, ld_pair, z_p, z_stride, D, N, S,
+                                             per, pc_sum, pc_sq, pi, pj, P, C, ld_c, s_off, goff,
+                                             (const uint32_t*)gent, K, E, Cg, ld_cg, sg_off, (double*)ws);
+  });
+  if (rc != NMGP_OK || !pc_sum || nsl == 1) return rc;
+  return fy_tri_reduce((const double*)ws, nsl, D, N, pc_sum, pc_sq, stream);
 }
 
 // the form without groups: the same launch, K = 0

@@ -8,10 +8,10 @@
 //   A = R R^T,  c = R^-1 b,  w_h = R^-1 l_h  (l_h = row h of L as a column),  mu_h = w_h^T c,  v_h = |w_h|^2 + s2
 // for every missing h.  A is D x D and positive definite whatever the mask, so the mask is a row weight only.
 //
-// One workgroup (4 waves) per (input n, slice of samples), L and A side by side in LDS in the tile layout of fy.hip
-// (fy_tiles.hpp; 2 x 72 KiB at D = 128) plus five D-vectors and the list of missing outputs (5.5 KiB): 149.5 KiB of
+// One workgroup (4 waves) per (input n, slice of samples), L and A side by side in LDS in the tile layout of
+// fy_tiles.hpp (2 x 72 KiB at D = 128) plus five D-vectors and the list of missing outputs (5.5 KiB): 149.5 KiB of
 // the CU's 160 KiB at D = 128.  A row without a missing entry returns at once.  Per sample:
-//   1. pair samples -> L tiles (bad-diagonal flag as pcorr.hip), V^-1 and mu_g -> LDS.
+//   1. pair samples -> L tiles (fy_load_L with its bad-diagonal flag), V^-1 and mu_g -> LDS.
 //   2. A's lower tiles on v_mfma_f64_16x16x4_f64, tile (ti, tj <= ti) = sum_{kt >= ti} L(kt, ti)^T diag(w) L(kt, tj)
 //      with w folded into the A operand (the operand pattern of Omega in pcorr.hip), tiles dealt round-robin; V^-1
 //      on the diagonal, 1 on the diagonal past D; b by two threads per column.
@@ -73,8 +73,7 @@ __global__ __launch_bounds__(kFyThreads) void ycond_accum_kernel(
   int* hl = (int*)(bv + NP);                                    // NP: the missing outputs of this row, ascending
   int* flags = hl + NP;                                         // [0], [1]: bad sample by parity; [2]: |H|
 
-  const int bid = blockIdx.x;
-  const int n = (bid % kFyXcds) * (n_blocks / kFyXcds) + bid / kFyXcds;   // as fy.hip: neighbours share an XCD
+  const int n = fy_block_input(n_blocks);
   if (n >= N) return;
   // offsets clamped to 0..E and made monotone: no table can make the kernel leave its buffers
   const int e0 = min(max(e_off[n], 0), E);
@@ -120,18 +119,7 @@ __global__ __launch_bounds__(kFyThreads) void ycond_accum_kernel(
 
   for (int s = s0; s < s1; ++s) {
     // ---- 1. pair samples -> L tiles; V^-1, mu_g
-    const double* zp = z_p + (int64_t)s * z_stride + n;
-#pragma unroll 1
-    for (int q = tid; q < Q; q += kFyThreads) {
-      const int i = fy_tri_row(q);
-      const int j = q - i * (i + 1) / 2;
-      double l = pair_mu[(int64_t)q * ld_pair + n] + pair_sd[(int64_t)q * ld_pair + n] * zp[(int64_t)q * N];
-      if (i == j) {
-        l = exp(l);
-        if (!(__builtin_isfinite(l) && l != 0.0)) flags[s & 1] = 1;
-      }
-      Lt[(fy_ntiles(i >> 4) + (j >> 4)) * kFyTileElems + fy_tile_off(i & 15, j & 15)] = l;
-    }
+    fy_load_L<true>(Lt, pair_mu, pair_sd, ld_pair, z_p + (int64_t)s * z_stride + n, n, N, Q, tid, &flags[s & 1]);
     if (tid < D) {
       const int64_t g = ((int64_t)s * N + n) * D + tid;
       const double v = var_g[g] + 1e-4;
@@ -395,27 +383,6 @@ __global__ __launch_bounds__(256) void ycond_reduce_kernel(const double* __restr
   }
 }
 
-template <int NT>
-static int ycond_launch(const double* pair_mu, const double* pair_sd, int64_t ld_pair, const double* z_p,
-                        int64_t z_stride, const double* mu_g, const double* var_g, const double* Y_obs, double s2,
-                        int D, int N, int S, int nsl, int per, const int32_t* e_off, int E, const YcOut& o,
-                        int64_t s_off, double* ws, hipStream_t s) {
-  const size_t smem = (size_t)(2 * fy_ntiles(NT) * kFyTileElems + 5 * NT * kFyTile) * sizeof(double) +
-                      (size_t)(NT * kFyTile + 4) * sizeof(int);
-  static bool attr_done = false;
-  if (!attr_done) {
-    (void)hipFuncSetAttribute((const void*)ycond_accum_kernel<NT>, hipFuncAttributeMaxDynamicSharedMemorySize,
-                              (int)smem);
-    attr_done = true;
-  }
-  const int n_blocks = (N + kFyXcds - 1) / kFyXcds * kFyXcds;
-  hipLaunchKernelGGL(ycond_accum_kernel<NT>, dim3((unsigned)n_blocks, (unsigned)nsl), dim3(kFyThreads), smem, s,
-                     pair_mu, pair_sd, ld_pair, z_p, z_stride, mu_g, var_g, Y_obs, s2, D, N, S, per, e_off, E, o, s_off,
-                     ws, n_blocks);
-  NMGP_CHECK_LAUNCH();
-  return NMGP_OK;
-}
-
 }  // namespace nmgp
 
 using namespace nmgp;
@@ -445,29 +412,15 @@ int nmgp_ycond_accum_f64(const double* pair_mu, const double* pair_sd, int64_t l
   if (Mu && ld < s_off + S) return NMGP_ERR_YCOND_ARG;
   int nsl, per;
   fy_slicing(N, S, &nsl, &per);
-  const int64_t need = nmgp_ycond_workspace_size(D, N, S);
-  if (need > 0 && (!ws || ws_bytes < need)) return NMGP_ERR_YCOND_ARG;
+  if (!ws_covers(nmgp_ycond_workspace_size(D, N, S), ws, ws_bytes)) return NMGP_ERR_YCOND_ARG;
   const YcOut o = {mu_sum, y2_sum, f2_sum, lse_max, lse_sum, Mu, Var, y_true};
-  const int nt = (D + kFyTile - 1) / kFyTile;
-  int rc;
-#define NMGP_YCOND_CASE(NT_)                                                                                       \
-  case NT_:                                                                                                        \
-    rc = ycond_launch<NT_>(pair_mu, pair_sd, ld_pair, z_p, z_stride, mu_g, var_g, Y_obs, s2, D, N, S, nsl, per,   \
-                           e_off, E, o, s_off, (double*)ws, stream);                                               \
-    break;
-  switch (nt) {
-    NMGP_YCOND_CASE(1)
-    NMGP_YCOND_CASE(2)
-    NMGP_YCOND_CASE(3)
-    NMGP_YCOND_CASE(4)
-    NMGP_YCOND_CASE(5)
-    NMGP_YCOND_CASE(6)
-    NMGP_YCOND_CASE(7)
-    NMGP_YCOND_CASE(8)
-    default:
-      return NMGP_ERR_YCOND_ARG;
-  }
-#undef NMGP_YCOND_CASE
+  const int rc = fy_dispatch_nt((D + kFyTile - 1) / kFyTile, NMGP_ERR_YCOND_ARG, [&](auto nt) {
+    constexpr int NT = decltype(nt)::value;
+    const size_t smem = (size_t)(2 * fy_ntiles(NT) * kFyTileElems + 5 * NT * kFyTile) * sizeof(double) +
+                        (size_t)(NT * kFyTile + 4) * sizeof(int);
+    return fy_launch<ycond_accum_kernel<NT>>(smem, N, nsl, stream, pair_mu, pair_sd, ld_pair, z_p, z_stride, mu_g,
+                                             var_g, Y_obs, s2, D, N, S, per, e_off, E, o, s_off, (double*)ws);
+  });
   if (rc != NMGP_OK) return rc;
   if (nsl > 1) {
     hipLaunchKernelGGL(ycond_reduce_kernel, dim3((unsigned)((E + 255) / 256)), dim3(256), 0, stream,

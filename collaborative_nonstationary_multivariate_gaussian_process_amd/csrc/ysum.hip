@@ -221,8 +221,7 @@ int nmgp_y_accum_f64(const double* pair_mu, const double* pair_sd, int64_t ld_pa
   // the samples (rows pass) and the D + 1 rows (moments pass) are dealt four to a workgroup along grid y
   if (S > kYRows * kYMaxGridY || D > kYRows * kYMaxGridY - 1) return NMGP_ERR_Y_ARG;
   const int nsl = y_slices(D, N, S);
-  const int64_t need = nmgp_y_workspace_size(D, N, S);
-  if (need > 0 && (!ws || ws_bytes < need)) return NMGP_ERR_Y_ARG;
+  if (!ws_covers(nmgp_y_workspace_size(D, N, S), ws, ws_bytes)) return NMGP_ERR_Y_ARG;
 
   const dim3 block(kYLanes, kYRows);
   const unsigned tiles = (unsigned)((N + kYLanes - 1) / kYLanes);

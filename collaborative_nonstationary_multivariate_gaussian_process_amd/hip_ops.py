@@ -1118,12 +1118,41 @@ def normal_(out, seed, counter=None, offset=0):
     return out
 
 
+def _pair_args(pair_mu, pair_sd, z_p):
+    """What the fused summaries' wrappers check of the operands they share -> (Q, N, D, S, z_stride): pair_mu /
+    pair_sd (Q, N) float64 with Q = D (D + 1) / 2, unit column stride and a common row stride >= N; z_p (S, >= Q N) a
+    column range of a noise block (unit column stride), whose row stride is z_stride (0 for a single sample)."""
+    for name, t in (("pair_mu", pair_mu), ("pair_sd", pair_sd), ("z_p", z_p)):
+        L.require_device(t, name)
+        assert t.dtype == torch.float64, name
+    Q, N = pair_mu.shape
+    D = int(((8 * Q + 1) ** 0.5 - 1) / 2 + 0.5)
+    assert D * (D + 1) // 2 == Q and pair_sd.shape == (Q, N)
+    assert pair_mu.stride(1) == 1 and pair_sd.stride(1) == 1 and pair_mu.stride(0) == pair_sd.stride(0) >= N
+    assert z_p.dim() == 2 and z_p.shape[1] >= Q * N and (z_p.stride(1) == 1 or z_p.shape[1] == 1)
+    S = z_p.shape[0]
+    return Q, N, D, S, (z_p.stride(0) if S > 1 else 0)
+
+
+def _slice_workspace(size_fn, D, N, S, device):
+    """Workspace of a kernel that slices the samples by fy_slicing (csrc/fy_tiles.hpp), for chunks of up to S
+    samples, or None when the samples are not sliced (N >= 256 or S == 1)."""
+    # a shorter last chunk can be cut into more slices than a full one: at most min(S, 512 // N), one sample each
+    need = max(size_fn(D, N, s) for s in {S, min(S, max(1, 512 // max(N, 1)))})
+    return torch.empty(need, dtype=torch.uint8, device=device) if need > 0 else None
+
+
+def _ws_or_alloc(ws, need, device):
+    """The caller's workspace where it holds `need` bytes, else one allocated here (the slices' partial sums)."""
+    if need > 0 and (ws is None or ws.numel() * ws.element_size() < need):
+        ws = torch.empty(need, dtype=torch.uint8, device=device)
+    return ws
+
+
 def fy_workspace(D, N, S, device):
     """Workspace of fy_accum_ for chunks of up to S samples (the slices' partial sums), or None when the samples
     are not sliced (N >= 256 or S == 1)."""
-    # a shorter last chunk can be cut into more slices than a full one: at most min(S, 512 // N), one sample each
-    need = max(L.lib().nmgp_fy_workspace_size(D, N, s) for s in {S, min(S, max(1, 512 // max(N, 1)))})
-    return torch.empty(need, dtype=torch.uint8, device=device) if need > 0 else None
+    return _slice_workspace(L.lib().nmgp_fy_workspace_size, D, N, S, device)
 
 
 def fy_accum_(pair_mu, pair_sd, G, z_p, z_f, sd_err, Y, corr_sum, corr_sq, ws=None):
@@ -1131,25 +1160,19 @@ def fy_accum_(pair_mu, pair_sd, G, z_p, z_f, sd_err, Y, corr_sum, corr_sq, ws=No
     (N, D, D) are accumulated onto.  pair_mu / pair_sd (Q, N) may have a row stride; G (S, D, N) is contiguous;
     z_p (S, >= Q N) and z_f (S, >= N D) are column ranges of one noise block (same row stride, unit column
     stride).  ws: fy_workspace(...) kept by a caller that runs several chunks, else allocated here."""
-    for name, t in (("pair_mu", pair_mu), ("pair_sd", pair_sd), ("G", G), ("z_p", z_p), ("z_f", z_f), ("Y", Y),
-                    ("corr_sum", corr_sum), ("corr_sq", corr_sq)):
+    Q, N, D, S, z_stride = _pair_args(pair_mu, pair_sd, z_p)
+    for name, t in (("G", G), ("z_f", z_f), ("Y", Y), ("corr_sum", corr_sum), ("corr_sq", corr_sq)):
         L.require_device(t, name)
         assert t.dtype == torch.float64, name
-    S, D, N = G.shape
+    assert G.shape == (S, D, N)                                                          # D is G's: Q must match it
     assert G.is_contiguous() and Y.is_contiguous() and corr_sum.is_contiguous() and corr_sq.is_contiguous()
-    assert pair_mu.shape == pair_sd.shape == (D * (D + 1) // 2, N)
-    assert pair_mu.stride(1) == 1 and pair_sd.stride(1) == 1 and pair_mu.stride(0) == pair_sd.stride(0) >= N
     assert Y.shape == (S, N, D) and corr_sum.shape == corr_sq.shape == (N, D, D)
-    Q = D * (D + 1) // 2
-    assert z_p.dim() == z_f.dim() == 2 and z_p.shape[0] == z_f.shape[0] == S
-    assert z_p.shape[1] >= Q * N and z_f.shape[1] >= N * D
+    assert z_f.dim() == 2 and z_f.shape[0] == S and z_f.shape[1] >= N * D
     assert S == 1 or z_p.stride(0) == z_f.stride(0)
-    assert (z_p.stride(1) == 1 or z_p.shape[1] == 1) and (z_f.stride(1) == 1 or z_f.shape[1] == 1)
-    z_stride = z_p.stride(0) if S > 1 else 0
+    assert z_f.stride(1) == 1 or z_f.shape[1] == 1
     lib = L.lib()
     need = lib.nmgp_fy_workspace_size(D, N, S)
-    if need > 0 and (ws is None or ws.numel() * ws.element_size() < need):
-        ws = torch.empty(need, dtype=torch.uint8, device=G.device)                      # slices' partial sums
+    ws = _ws_or_alloc(ws, need, G.device)
     L.check(lib.nmgp_fy_accum_f64(L.ptr(pair_mu), L.ptr(pair_sd), pair_mu.stride(0), L.ptr(G), L.ptr(z_p), L.ptr(z_f),
                                   int(z_stride), float(sd_err), D, N, S, L.ptr(Y), L.ptr(corr_sum), L.ptr(corr_sq),
                                   L.ptr(ws) if need > 0 else None, need, L.stream_handle()), "fy_accum")
@@ -1160,24 +1183,17 @@ def corr_collect_(pair_mu, pair_sd, z_p, pi, pj, C, s_off=0):
     written for the S samples of z_p; nothing is accumulated.  pair_mu / pair_sd (Q, N) may have a row stride;
     z_p (S, >= Q N) is a column range of a noise block (unit column stride); pi / pj (P) int32 device vectors;
     C (P, N, ld_c) contiguous with ld_c >= s_off + S."""
-    for name, t in (("pair_mu", pair_mu), ("pair_sd", pair_sd), ("z_p", z_p), ("C", C)):
-        L.require_device(t, name)
-        assert t.dtype == torch.float64, name
+    Q, N, D, S, z_stride = _pair_args(pair_mu, pair_sd, z_p)
+    L.require_device(C, "C")
+    assert C.dtype == torch.float64, "C"
     for name, t in (("pi", pi), ("pj", pj)):
         L.require_device(t, name)
         assert t.dtype == torch.int32 and t.dim() == 1 and t.is_contiguous(), name
-    Q, N = pair_mu.shape
-    D = int(((8 * Q + 1) ** 0.5 - 1) / 2 + 0.5)
-    assert D * (D + 1) // 2 == Q and pair_sd.shape == (Q, N)
-    assert pair_mu.stride(1) == 1 and pair_sd.stride(1) == 1 and pair_mu.stride(0) == pair_sd.stride(0) >= N
     P = pi.numel()
     assert pj.numel() == P
     assert C.dim() == 3 and C.shape[:2] == (P, N) and C.is_contiguous()
-    assert z_p.dim() == 2 and z_p.shape[1] >= Q * N and (z_p.stride(1) == 1 or z_p.shape[1] == 1)
-    S = z_p.shape[0]
     s_off = int(s_off)
     assert 0 <= s_off and s_off + S <= C.shape[2]
-    z_stride = z_p.stride(0) if S > 1 else 0
     L.check(L.lib().nmgp_corr_collect_f64(L.ptr(pair_mu), L.ptr(pair_sd), pair_mu.stride(0), L.ptr(z_p), int(z_stride),
                                           L.ptr(pi), L.ptr(pj), P, D, N, S, L.ptr(C), C.shape[2], s_off,
                                           L.stream_handle()), "corr_collect")
@@ -1187,9 +1203,7 @@ def corr_collect_(pair_mu, pair_sd, z_p, pi, pj, C, s_off=0):
 def pcorr_workspace(D, N, S, device):
     """Workspace of pcorr_accum_ for chunks of up to S samples (the slices' partial sums), or None when the samples
     are not sliced (N >= 256 or S == 1)."""
-    # as fy_workspace: a shorter last chunk can be cut into more slices than a full one
-    need = max(L.lib().nmgp_pcorr_workspace_size(D, N, s) for s in {S, min(S, max(1, 512 // max(N, 1)))})
-    return torch.empty(need, dtype=torch.uint8, device=device) if need > 0 else None
+    return _slice_workspace(L.lib().nmgp_pcorr_workspace_size, D, N, S, device)
 
 
 def pcorr_accum_(pair_mu, pair_sd, z_p, pc_sum=None, pc_sq=None, pi=None, pj=None, C=None, s_off=0, ws=None,
@@ -1202,16 +1216,7 @@ def pcorr_accum_(pair_mu, pair_sd, z_p, pc_sum=None, pc_sq=None, pi=None, pj=Non
     means of the sample's partial correlations are written to Cg[k, n, sg_off + s] (Cg (K, N, ld_cg) contiguous).
     Sums, pair list and groups are independent of each other.  ws: pcorr_workspace(...) kept by a caller that runs
     several chunks, else allocated here."""
-    for name, t in (("pair_mu", pair_mu), ("pair_sd", pair_sd), ("z_p", z_p)):
-        L.require_device(t, name)
-        assert t.dtype == torch.float64, name
-    Q, N = pair_mu.shape
-    D = int(((8 * Q + 1) ** 0.5 - 1) / 2 + 0.5)
-    assert D * (D + 1) // 2 == Q and pair_sd.shape == (Q, N)
-    assert pair_mu.stride(1) == 1 and pair_sd.stride(1) == 1 and pair_mu.stride(0) == pair_sd.stride(0) >= N
-    assert z_p.dim() == 2 and z_p.shape[1] >= Q * N and (z_p.stride(1) == 1 or z_p.shape[1] == 1)
-    S = z_p.shape[0]
-    z_stride = z_p.stride(0) if S > 1 else 0
+    Q, N, D, S, z_stride = _pair_args(pair_mu, pair_sd, z_p)
     assert (pc_sum is None) == (pc_sq is None), "pc_sum and pc_sq go together"
     sums = pc_sum is not None
     if sums:
@@ -1238,8 +1243,7 @@ def pcorr_accum_(pair_mu, pair_sd, z_p, pc_sum=None, pc_sq=None, pi=None, pj=Non
     assert sums or P > 0 or K > 0, "nothing to do: neither sums nor a pair list nor groups"
     lib = L.lib()
     need = lib.nmgp_pcorr_workspace_size(D, N, S) if sums else 0
-    if need > 0 and (ws is None or ws.numel() * ws.element_size() < need):
-        ws = torch.empty(need, dtype=torch.uint8, device=z_p.device)                    # slices' partial sums
+    ws = _ws_or_alloc(ws, need, z_p.device)
     head = (L.ptr(pair_mu), L.ptr(pair_sd), pair_mu.stride(0), L.ptr(z_p), int(z_stride), D, N, S, L.ptr(pc_sum),
             L.ptr(pc_sq), L.ptr(pi) if P else None, L.ptr(pj) if P else None, P, L.ptr(C) if P else None, ld_c, s_off)
     tail = (L.ptr(ws) if need > 0 else None, need, L.stream_handle())
@@ -1254,9 +1258,7 @@ def pcorr_accum_(pair_mu, pair_sd, z_p, pc_sum=None, pc_sq=None, pi=None, pj=Non
 def ycond_workspace(D, N, S, device):
     """Workspace of ycond_accum_ for chunks of up to S samples (the slices' partial sums), or None when the samples
     are not sliced (N >= 256 or S == 1)."""
-    # as pcorr_workspace: a shorter last chunk can be cut into more slices than a full one
-    need = max(L.lib().nmgp_ycond_workspace_size(D, N, s) for s in {S, min(S, max(1, 512 // max(N, 1)))})
-    return torch.empty(need, dtype=torch.uint8, device=device) if need > 0 else None
+    return _slice_workspace(L.lib().nmgp_ycond_workspace_size, D, N, S, device)
 
 
 def missing_table(Y_obs):
@@ -1279,17 +1281,11 @@ def ycond_accum_(pair_mu, pair_sd, z_p, mu_g, var_g, Y_obs, s2, e_off, mu_sum, y
     of log N(y_true | mu, v) is advanced where y_true is finite; with Mu / Var (ld >= s_off + S, E) the samples'
     mu and v are written to row s_off + s.  ws: ycond_workspace(...) kept by a caller that runs several chunks,
     else allocated here."""
-    for name, t in (("pair_mu", pair_mu), ("pair_sd", pair_sd), ("z_p", z_p), ("mu_g", mu_g), ("var_g", var_g),
-                    ("Y_obs", Y_obs), ("mu_sum", mu_sum), ("y2_sum", y2_sum), ("f2_sum", f2_sum)):
+    Q, N, D, S, z_stride = _pair_args(pair_mu, pair_sd, z_p)
+    for name, t in (("mu_g", mu_g), ("var_g", var_g), ("Y_obs", Y_obs), ("mu_sum", mu_sum), ("y2_sum", y2_sum),
+                    ("f2_sum", f2_sum)):
         L.require_device(t, name)
         assert t.dtype == torch.float64, name
-    Q, N = pair_mu.shape
-    D = int(((8 * Q + 1) ** 0.5 - 1) / 2 + 0.5)
-    assert D * (D + 1) // 2 == Q and pair_sd.shape == (Q, N)
-    assert pair_mu.stride(1) == 1 and pair_sd.stride(1) == 1 and pair_mu.stride(0) == pair_sd.stride(0) >= N
-    assert z_p.dim() == 2 and z_p.shape[1] >= Q * N and (z_p.stride(1) == 1 or z_p.shape[1] == 1)
-    S = z_p.shape[0]
-    z_stride = z_p.stride(0) if S > 1 else 0
     for name, t in (("mu_g", mu_g), ("var_g", var_g)):
         assert t.shape == (S, N, D) and t.is_contiguous(), name
     assert Y_obs.shape == (N, D) and Y_obs.is_contiguous()
@@ -1313,8 +1309,7 @@ def ycond_accum_(pair_mu, pair_sd, z_p, mu_g, var_g, Y_obs, s2, e_off, mu_sum, y
         assert Var.shape[0] == ld and 0 <= s_off and s_off + S <= ld
     lib = L.lib()
     need = lib.nmgp_ycond_workspace_size(D, N, S) if E > 0 else 0
-    if need > 0 and (ws is None or ws.numel() * ws.element_size() < need):
-        ws = torch.empty(need, dtype=torch.uint8, device=z_p.device)                    # slices' partial sums
+    ws = _ws_or_alloc(ws, need, z_p.device)
     L.check(lib.nmgp_ycond_accum_f64(L.ptr(pair_mu), L.ptr(pair_sd), pair_mu.stride(0), L.ptr(z_p), int(z_stride),
                                      L.ptr(mu_g), L.ptr(var_g), L.ptr(Y_obs), float(s2), D, N, S, L.ptr(e_off), E,
                                      L.ptr(mu_sum), L.ptr(y2_sum), L.ptr(f2_sum), L.ptr(y_true), L.ptr(lse_max),
@@ -1366,18 +1361,9 @@ def corr_group_(pair_mu, pair_sd, z_p, goff, gent, C, s_off=0):
     written for the S samples of z_p and the K groups of the table (goff, gent) = group_table(...); nothing is
     accumulated.  pair_mu / pair_sd (Q, N) may have a row stride; z_p (S, >= Q N) is a column range of a noise block
     (unit column stride); C (K, N, ld_c) contiguous with ld_c >= s_off + S."""
-    for name, t in (("pair_mu", pair_mu), ("pair_sd", pair_sd), ("z_p", z_p)):
-        L.require_device(t, name)
-        assert t.dtype == torch.float64, name
-    Q, N = pair_mu.shape
-    D = int(((8 * Q + 1) ** 0.5 - 1) / 2 + 0.5)
-    assert D * (D + 1) // 2 == Q and pair_sd.shape == (Q, N)
-    assert pair_mu.stride(1) == 1 and pair_sd.stride(1) == 1 and pair_mu.stride(0) == pair_sd.stride(0) >= N
-    assert z_p.dim() == 2 and z_p.shape[1] >= Q * N and (z_p.stride(1) == 1 or z_p.shape[1] == 1)
-    S = z_p.shape[0]
+    Q, N, D, S, z_stride = _pair_args(pair_mu, pair_sd, z_p)
     s_off = int(s_off)
     K, E = _check_group_args(goff, gent, C, N, S, s_off, "C")
-    z_stride = z_p.stride(0) if S > 1 else 0
     L.check(L.lib().nmgp_corr_group_f64(L.ptr(pair_mu), L.ptr(pair_sd), pair_mu.stride(0), L.ptr(z_p), int(z_stride),
                                         D, N, S, L.ptr(goff), L.ptr(gent), K, E, L.ptr(C), C.shape[2], s_off,
                                         L.stream_handle()), "corr_group")
@@ -1422,8 +1408,9 @@ def y_accum_(pair_mu, pair_sd, G, z_p, z_f, I, sd_err, Y, F, F_sum, F_sq, L_sum,
     contiguous; I (N) int64 output ids; z_p (S, >= Q N) and z_f (S, >= N) are column ranges of one noise block
     (same row stride, unit column stride).  ws: y_workspace(...) kept by a caller that runs several chunks, else
     allocated here."""
-    named = [("pair_mu", pair_mu), ("pair_sd", pair_sd), ("G", G), ("z_p", z_p), ("z_f", z_f), ("Y", Y), ("F", F),
-             ("F_sum", F_sum), ("F_sq", F_sq), ("L_sum", L_sum), ("L_sq", L_sq), ("G_sum", G_sum), ("G_sq", G_sq)]
+    Q, N, D, S, z_stride = _pair_args(pair_mu, pair_sd, z_p)
+    named = [("G", G), ("z_f", z_f), ("Y", Y), ("F", F), ("F_sum", F_sum), ("F_sq", F_sq), ("L_sum", L_sum),
+             ("L_sq", L_sq), ("G_sum", G_sum), ("G_sq", G_sq)]
     if y is not None:
         assert lse_max is not None and lse_sum is not None, "y needs the lse_max / lse_sum state"
         named += [("y", y), ("lse_max", lse_max), ("lse_sum", lse_sum)]
@@ -1432,25 +1419,19 @@ def y_accum_(pair_mu, pair_sd, G, z_p, z_f, I, sd_err, Y, F, F_sum, F_sq, L_sum,
         assert t.dtype == torch.float64, name
     L.require_device(I, "I")
     assert I.dtype == torch.int64 and I.is_contiguous()
-    S, D, N = G.shape
-    Q = D * (D + 1) // 2
+    assert G.shape == (S, D, N)                                                          # D is G's: Q must match it
     assert I.shape == (N,)
-    assert G.is_contiguous() and all(t.is_contiguous() for _, t in named[5:])
-    assert pair_mu.shape == pair_sd.shape == (Q, N)
-    assert pair_mu.stride(1) == 1 and pair_sd.stride(1) == 1 and pair_mu.stride(0) == pair_sd.stride(0) >= N
+    assert G.is_contiguous() and all(t.is_contiguous() for _, t in named[2:])
     assert Y.shape == F.shape == (S, N) and F_sum.shape == F_sq.shape == (N,)
     assert L_sum.shape == L_sq.shape == (N, D) and G_sum.shape == G_sq.shape == (D, N)
     if y is not None:
         assert y.shape == lse_max.shape == lse_sum.shape == (N,)
-    assert z_p.dim() == z_f.dim() == 2 and z_p.shape[0] == z_f.shape[0] == S
-    assert z_p.shape[1] >= Q * N and z_f.shape[1] >= N
+    assert z_f.dim() == 2 and z_f.shape[0] == S and z_f.shape[1] >= N
     assert S == 1 or z_p.stride(0) == z_f.stride(0)
-    assert (z_p.stride(1) == 1 or z_p.shape[1] == 1) and (z_f.stride(1) == 1 or z_f.shape[1] == 1)
-    z_stride = z_p.stride(0) if S > 1 else 0
+    assert z_f.stride(1) == 1 or z_f.shape[1] == 1
     lib = L.lib()
     need = lib.nmgp_y_workspace_size(D, N, S)
-    if need > 0 and (ws is None or ws.numel() * ws.element_size() < need):
-        ws = torch.empty(need, dtype=torch.uint8, device=G.device)                      # slices' partial sums
+    ws = _ws_or_alloc(ws, need, G.device)
     L.check(lib.nmgp_y_accum_f64(L.ptr(pair_mu), L.ptr(pair_sd), pair_mu.stride(0), L.ptr(G), L.ptr(z_p), L.ptr(z_f),
                                  int(z_stride), L.ptr(I), L.ptr(y), float(sd_err), D, N, S, L.ptr(Y), L.ptr(F),
                                  L.ptr(F_sum), L.ptr(F_sq), L.ptr(L_sum), L.ptr(L_sq), L.ptr(G_sum), L.ptr(G_sq),

@@ -231,20 +231,50 @@ def _sampling_setup(model, x):
     return st
 
 
+def _noise_layout(st, fy):
+    """The noise of one sample, in the reference's call order: [z_v M][z_t N][z_p Q N][z_g D N][z_f], z_f being N D
+    wide for the sample_FY family (fy=True) and N wide for the sample_Y family -> (per, o_p, o_g, o_f): the length of
+    the block and the offsets of z_p, z_g and z_f in it."""
+    N, D, M = st["N"], st["D"], st["M"]
+    o_p = M + N
+    o_g = o_p + len(st["pairs"]) * N
+    o_f = o_g + D * N
+    return o_f + (N * D if fy else N), o_p, o_g, o_f
+
+
+def _chunks(draws, n_sample, chunk, per, rewind=False):
+    """The walk over the noise stream in chunks of up to `chunk` samples: yields (done, S, zc), zc the (S, per) noise
+    of the samples done .. done + S.  rewind=True starts the stream over first, so the walk sees the noise of the
+    walk before it."""
+    if rewind:
+        draws.rewind()
+    done = 0
+    while done < n_sample:
+        S = min(chunk, n_sample - done)
+        yield done, S, draws.take(S, per)
+        done += S
+
+
+def _check_sampling_args(quantiles, n_sample):
+    """quantiles and n_sample of the summaries -> ([float], int), ValueError where they make no sense."""
+    qs = [float(q) for q in quantiles]
+    if any(not 0.0 <= q <= 1.0 for q in qs):
+        raise ValueError("quantiles must lie in [0, 1]")
+    n_sample = int(n_sample)
+    if n_sample < 1:
+        raise ValueError("n_sample must be at least 1")
+    return qs, n_sample
+
+
 def _sample_T_moments(st, zc):
     """The part of a chunk that every sampler shares up to the latent's marginals: tilde-ell T (S, N) and, given it,
     the MGP_d marginals of the latent G, mu_g (S, N, D) and var_g (S, D, N), of S samples from their noise block zc
-    (S, per-sample noise, laid out [z_v M][z_t N][z_p Q N][z_g D N][z_f ...]).  Also returns the column offsets of
-    z_p, z_g and z_f in zc."""
+    (S, per-sample noise, laid out as _noise_layout says).  Also returns the column offsets of z_p, z_g and z_f in
+    zc."""
     N, D, M = st["N"], st["D"], st["M"]
-    Q = len(st["pairs"])
     S = zc.shape[0]
-    o = 0
-    z_v = zc[:, o:o + M]; o += M
-    z_t = zc[:, o:o + N]; o += N
-    o_p = o; o += Q * N
-    o_g = o; o += D * N
-    o_f = o
+    _, o_p, o_g, o_f = _noise_layout(st, False)                          # the offsets do not depend on z_f's width
+    z_v, z_t = zc[:, :M], zc[:, M:o_p]
     # v = mu_v + chol(Sigma_v + 1e-4 I) z_v ; t = P_t v + sqrt(var_t + 1e-4) z_t   (JGP_S)
     V = st["mu_v"].reshape(1, M) + H.matmul(z_v.contiguous(), st["Cv"], transB=True, maskB=L.B_UPPER)
     T = H.matmul(V, st["Pt"], transB=True) + torch.sqrt(st["var_t"] + JIT).reshape(1, N) * z_t
@@ -308,25 +338,18 @@ def sample_Y(model, X_list, n_sample=1000, index=None, noise_tape=None):
     """NMGP.sample_Y (code/nmgp_dsvi.py:406-490) on the device -> (Ys (S, N), Ls (S, N, D),
     Gs (S, D, N), tilde_ells (S, N)), torch tensors on the model's device."""
     dev = model.device_
-    xs = [torch.as_tensor(x).reshape(-1).to(F64) for x in X_list]
-    ids = list(range(len(xs))) if index is None else list(index)
-    I = torch.cat([torch.full((x.shape[0],), int(j), dtype=torch.long) for x, j in zip(xs, ids)]).to(dev)
-    x = torch.cat(xs).to(dev).reshape(-1, 1).contiguous()
+    x, I = prepare_inputs(model, X_list, index)
     st = _sampling_setup(model, x)
-    N, D, M = st["N"], st["D"], st["M"]
-    per = M + N + len(st["pairs"]) * N + D * N + N
-    draws = _Draws(dev, noise_tape)
+    N, M = st["N"], st["M"]
+    per = _noise_layout(st, False)[0]
     sd_err = (st["s2_err"] + JIT) ** 0.5
     rows = torch.arange(N, device=dev)
     Ys, Ls, Gs, Ts = [], [], [], []
-    done = 0
-    while done < n_sample:
-        S = min(_chunk_size(n_sample, N, M), n_sample - done)
-        T, Lfull, G, z_f = _sample_chunk(st, draws.take(S, per), fy=False)
+    for _, _, zc in _chunks(_Draws(dev, noise_tape), n_sample, _chunk_size(n_sample, N, M), per):
+        T, Lfull, G, z_f = _sample_chunk(st, zc, fy=False)
         l = Lfull.permute(0, 3, 1, 2)[:, rows, I]                       # (S, N, D): row I_n of L
         F = (l * G.transpose(1, 2)).sum(2)
         Ys.append(F + sd_err * z_f), Ls.append(l), Gs.append(G), Ts.append(T)
-        done += S
     return torch.cat(Ys), torch.cat(Ls), torch.cat(Gs), torch.cat(Ts)
 
 
@@ -336,21 +359,16 @@ def sample_FY(model, x, n_sample=1000, noise_tape=None):
     dev = model.device_
     x = torch.as_tensor(x).reshape(-1, 1).to(F64).to(dev).contiguous()
     st = _sampling_setup(model, x)
-    N, D, M = st["N"], st["D"], st["M"]
-    per = M + N + len(st["pairs"]) * N + D * N + N * D
-    draws = _Draws(dev, noise_tape)
+    per = _noise_layout(st, True)[0]
     sd_err = (st["s2_err"] + JIT) ** 0.5
     Ts, Ys, Cs = [], [], []
-    done = 0
-    while done < n_sample:
-        S = min(_chunk_size(n_sample, N, M), n_sample - done)
-        T, Lfull, G, z_f = _sample_chunk(st, draws.take(S, per), fy=True)
+    for _, _, zc in _chunks(_Draws(dev, noise_tape), n_sample, _chunk_size(n_sample, st["N"], st["M"]), per):
+        T, Lfull, G, z_f = _sample_chunk(st, zc, fy=True)
         Ln = Lfull.permute(0, 3, 1, 2)                                   # (S, N, D, D)
         F = torch.matmul(Ln, G.transpose(1, 2).unsqueeze(3))[..., 0]     # (S, N, D)
         cov = torch.matmul(Ln, Ln.transpose(2, 3))
         invstd = torch.sqrt(torch.diag_embed(1.0 / torch.diagonal(cov, dim1=-2, dim2=-1)))
         Ts.append(T), Ys.append(F + sd_err * z_f), Cs.append(torch.matmul(torch.matmul(invstd, cov), invstd))
-        done += S
     return torch.cat(Ts), torch.cat(Ys), torch.cat(Cs)
 
 
@@ -440,6 +458,16 @@ def groups_from_labels(labels, between=True):
     return groups, names
 
 
+def _pop_sd(sq_mean, mean):
+    return torch.sqrt(torch.clamp(sq_mean - mean * mean, min=0.0))
+
+
+def _lpd(lse_max, lse_sum, ok, n_sample):
+    """log mean_s exp(ll_s) from the log-sum-exp state of the n_sample log densities; NaN where not ok (unscored)."""
+    nan = torch.full((), float("nan"), dtype=F64, device=ok.device)
+    return torch.where(ok, lse_max + torch.log(lse_sum) - float(np.log(n_sample)), nan)
+
+
 def _group_stats(Gb, qs):
     """Mean, population sd and quantiles over the samples of the collected group means Gb (groups, N, S) ->
     (N, groups), (N, groups), (len(qs), N, groups).  Mean and sd are taken group by group on (N, S) blocks, so
@@ -471,6 +499,56 @@ def _band_quantiles(C, qs):
             rows.append(torch.where(bad, torch.full_like(r, float("nan")), r))
         out = torch.stack(rows)
     return out.reshape(len(qs), pb, N).permute(0, 2, 1)
+
+
+def _pair_bands(walk, st, o_p, qs, pi, pj, pb, Cb, Pb):
+    """The quantile bands of the P listed pairs, pb pairs at a time -> (cq, pq), each (len(qs), N, P); pq is None
+    without Pb.  The main pass has collected the first batch into Cb (pb, N, S) and, with partial, Pb; every further
+    batch walks the noise stream again (walk() yields _chunks from position 0) and launches only the collectors."""
+    P, N = pi.numel(), Cb.shape[1]
+    cq = torch.empty(len(qs), N, P, dtype=F64, device=Cb.device)
+    pq = None if Pb is None else torch.empty_like(cq)
+    for p0 in range(0, P, pb):
+        p1 = min(P, p0 + pb)
+        if p0 > 0:
+            for done, _, zc in walk():
+                H.corr_collect_(st["pair_mu"], st["pair_sd"], zc[:, o_p:], pi[p0:p1], pj[p0:p1], Cb[:p1 - p0],
+                                s_off=done)
+                if Pb is not None:
+                    H.pcorr_accum_(st["pair_mu"], st["pair_sd"], zc[:, o_p:], pi=pi[p0:p1], pj=pj[p0:p1],
+                                   C=Pb[:p1 - p0], s_off=done)
+                del zc                                                    # freed before the next chunk is drawn
+        cq[:, :, p0:p1] = _band_quantiles(Cb[:p1 - p0], qs)
+        if Pb is not None:
+            pq[:, :, p0:p1] = _band_quantiles(Pb[:p1 - p0], qs)
+    return cq, pq
+
+
+def _group_bands(walk, st, o_p, qs, tabs, Gb, PGb):
+    """Mean, sd and quantiles of the group means, one table of tabs at a time -> (stats, pstats), each the list of
+    the batches' _group_stats; pstats is empty without PGb.  The main pass has collected the groups of tabs[0] into
+    Gb (and, with partial, PGb); every further table walks the noise stream again and launches only the group
+    kernels."""
+    stats, pstats = [], []
+    for b, (goff, gent) in enumerate(tabs):
+        kb = goff.numel() - 1
+        if b > 0:
+            for done, _, zc in walk():
+                H.corr_group_(st["pair_mu"], st["pair_sd"], zc[:, o_p:], goff, gent, Gb[:kb], s_off=done)
+                if PGb is not None:
+                    H.pcorr_accum_(st["pair_mu"], st["pair_sd"], zc[:, o_p:], goff=goff, gent=gent, Cg=PGb[:kb],
+                                   sg_off=done)
+                del zc                                                    # freed before the next chunk is drawn
+        stats.append(_group_stats(Gb[:kb], qs))
+        if PGb is not None:
+            pstats.append(_group_stats(PGb[:kb], qs))
+    return stats, pstats
+
+
+def _group_keys(prefix, stats):
+    """The batches' (mean, sd, quantiles) side by side along the group axis, under the keys of summarize_FY."""
+    return {prefix + "_mean": torch.cat([v[0] for v in stats], 1), prefix + "_sd": torch.cat([v[1] for v in stats], 1),
+            prefix + "_quantiles": torch.cat([v[2] for v in stats], 2)}
 
 
 def summarize_FY(model, x, n_sample=1000, quantiles=(0.025, 0.975), noise_tape=None, keep_samples=False,
@@ -520,12 +598,7 @@ def summarize_FY(model, x, n_sample=1000, quantiles=(0.025, 0.975), noise_tape=N
     the noise stream again and launches only the group kernels.  The result does not depend on band_bytes.  With
     keep_samples=True the buffer is the full (K, N, S), whatever band_bytes says.  Anything else than None or such
     a sequence raises ValueError before any device work; with None nothing is launched or returned."""
-    qs = [float(q) for q in quantiles]
-    if any(not 0.0 <= q <= 1.0 for q in qs):
-        raise ValueError("quantiles must lie in [0, 1]")
-    n_sample = int(n_sample)
-    if n_sample < 1:
-        raise ValueError("n_sample must be at least 1")
+    qs, n_sample = _check_sampling_args(quantiles, n_sample)
     pairs_t = None if corr_pairs is None else _parse_corr_pairs(corr_pairs, model.D)
     groups = None if corr_groups is None else _parse_corr_groups(corr_groups, model.D)
     dev = model.device_
@@ -534,8 +607,7 @@ def summarize_FY(model, x, n_sample=1000, quantiles=(0.025, 0.975), noise_tape=N
     N, D, M = st["N"], st["D"], st["M"]
     if D > 128:
         raise ValueError("summarize_FY: the fused kernel holds L in one workgroup's LDS, D <= 128")
-    Q = len(st["pairs"])
-    per = M + N + Q * N + D * N + N * D
+    per, o_p, _, o_f = _noise_layout(st, True)
     draws = _Draws(dev, noise_tape)
     sd_err = (st["s2_err"] + JIT) ** 0.5
     Ts = torch.empty(n_sample, N, dtype=F64, device=dev)
@@ -545,6 +617,7 @@ def summarize_FY(model, x, n_sample=1000, quantiles=(0.025, 0.975), noise_tape=N
     chunk = _chunk_size(n_sample, N, M)
     ws = H.fy_workspace(D, N, chunk, dev)
     P = 0 if pairs_t is None else pairs_t.shape[0]
+    Pb = PGb = None                                                      # the partial-correlation batch buffers
     if partial:
         psum = torch.zeros(N, D, D, dtype=F64, device=dev)
         psq = torch.zeros(N, D, D, dtype=F64, device=dev)
@@ -554,25 +627,19 @@ def summarize_FY(model, x, n_sample=1000, quantiles=(0.025, 0.975), noise_tape=N
         pij = pairs_t.to(torch.int32).to(dev)
         pi, pj = pij[:, 0].contiguous(), pij[:, 1].contiguous()
         Cb = torch.empty(pb, N, n_sample, dtype=F64, device=dev)
-        cq = torch.empty(len(qs), N, P, dtype=F64, device=dev)
         if partial:
             Pb = torch.empty(pb, N, n_sample, dtype=F64, device=dev)
-            pq = torch.empty(len(qs), N, P, dtype=F64, device=dev)
     K = 0 if groups is None else len(groups)
     if K:
         # groups per batch; the kept samples are one buffer of all the groups
         gb = K if keep_samples else min(K, max(1, int(band_bytes) // (8 * n_sample * N)))
         tabs = [H.group_table(groups[k0:k0 + gb], D, dev) for k0 in range(0, K, gb)]
         Gb = torch.empty(gb, N, n_sample, dtype=F64, device=dev)
-        gstats = [[], [], []]                                            # mean, sd, quantiles, batch by batch
         if partial:
             PGb = torch.empty(gb, N, n_sample, dtype=F64, device=dev)
-            pgstats = [[], [], []]
-    done = 0
-    while done < n_sample:
-        S = min(chunk, n_sample - done)
-        zc = draws.take(S, per)
-        T, G, o_p, o_f = _sample_TG(st, zc)
+    # ---- the main pass: the sampling head and the fused tails of every chunk, the first batches riding along
+    for done, S, zc in _chunks(draws, n_sample, chunk, per):
+        T, G, _, _ = _sample_TG(st, zc)
         Ts[done:done + S] = T
         H.fy_accum_(st["pair_mu"], st["pair_sd"], G.contiguous(), zc[:, o_p:], zc[:, o_f:], sd_err,
                     Ys[done:done + S], csum, csq, ws=ws)
@@ -586,84 +653,40 @@ def summarize_FY(model, x, n_sample=1000, quantiles=(0.025, 0.975), noise_tape=N
             if K:
                 kw.update(goff=tabs[0][0], gent=tabs[0][1], Cg=PGb, sg_off=done)
             H.pcorr_accum_(st["pair_mu"], st["pair_sd"], zc[:, o_p:], psum, psq, ws=pws, **kw)
-        done += S
     mean = csum / n_sample
     out = {"tilde_ell_mean": Ts.mean(0), "tilde_ell_quantiles": _quantiles_dim0(Ts, qs),
            "Y_mean": Ys.mean(0), "Y_quantiles": _quantiles_dim0(Ys, qs),
-           "corr_mean": mean, "corr_sd": torch.sqrt(torch.clamp(csq / n_sample - mean * mean, min=0.0))}
+           "corr_mean": mean, "corr_sd": _pop_sd(csq / n_sample, mean)}
     if partial:
         pmean = psum / n_sample
-        out["pcorr_mean"] = pmean
-        out["pcorr_sd"] = torch.sqrt(torch.clamp(psq / n_sample - pmean * pmean, min=0.0))
+        out["pcorr_mean"], out["pcorr_sd"] = pmean, _pop_sd(psq / n_sample, pmean)
     if keep_samples:
         out["Ys"], out["tilde_ells"] = Ys, Ts
+    walk = lambda: _chunks(draws, n_sample, chunk, per, rewind=True)
+    # ---- the pair bands: the chunk's G, T and noise are released before the further batches walk the stream again
     if pairs_t is not None:
         if P:
             del G, T, zc
-            o_p = M + N                                                   # the noise layout of _sample_TG
-            cq[:, :, :pb] = _band_quantiles(Cb, qs)
-            if partial:
-                pq[:, :, :pb] = _band_quantiles(Pb, qs)
-            for p0 in range(pb, P, pb):
-                p1 = min(P, p0 + pb)
-                draws.rewind()
-                done = 0
-                while done < n_sample:
-                    S = min(chunk, n_sample - done)
-                    zc = draws.take(S, per)
-                    H.corr_collect_(st["pair_mu"], st["pair_sd"], zc[:, o_p:], pi[p0:p1], pj[p0:p1], Cb[:p1 - p0],
-                                    s_off=done)
-                    if partial:
-                        H.pcorr_accum_(st["pair_mu"], st["pair_sd"], zc[:, o_p:], pi=pi[p0:p1], pj=pj[p0:p1],
-                                       C=Pb[:p1 - p0], s_off=done)
-                    done += S
-                    del zc
-                cq[:, :, p0:p1] = _band_quantiles(Cb[:p1 - p0], qs)
-                if partial:
-                    pq[:, :, p0:p1] = _band_quantiles(Pb[:p1 - p0], qs)
+            cq, pq = _pair_bands(walk, st, o_p, qs, pi, pj, pb, Cb, Pb)
         else:
             cq = torch.empty(len(qs), N, 0, dtype=F64, device=dev)
             pq = torch.empty(len(qs), N, 0, dtype=F64, device=dev)
         out["corr_pairs"], out["corr_quantiles"] = pairs_t.to(dev), cq
         if partial:
             out["pcorr_quantiles"] = pq
+    # ---- the group bands, likewise
     if K:
         G = T = zc = None
-        o_p = M + N                                                       # the noise layout of _sample_TG
-        for b, (goff, gent) in enumerate(tabs):
-            kb = goff.numel() - 1
-            if b > 0:
-                draws.rewind()
-                done = 0
-                while done < n_sample:
-                    S = min(chunk, n_sample - done)
-                    zc = draws.take(S, per)
-                    H.corr_group_(st["pair_mu"], st["pair_sd"], zc[:, o_p:], goff, gent, Gb[:kb], s_off=done)
-                    if partial:
-                        H.pcorr_accum_(st["pair_mu"], st["pair_sd"], zc[:, o_p:], goff=goff, gent=gent, Cg=PGb[:kb],
-                                       sg_off=done)
-                    done += S
-                    del zc
-            for acc, v in zip(gstats, _group_stats(Gb[:kb], qs)):
-                acc.append(v)
-            if partial:
-                for acc, v in zip(pgstats, _group_stats(PGb[:kb], qs)):
-                    acc.append(v)
+        stats, pstats = _group_bands(walk, st, o_p, qs, tabs, Gb, PGb)
         out["corr_group_sizes"] = torch.tensor([len(g) for g in groups], dtype=torch.long, device=dev)
-        out["corr_group_mean"], out["corr_group_sd"] = torch.cat(gstats[0], 1), torch.cat(gstats[1], 1)
-        out["corr_group_quantiles"] = torch.cat(gstats[2], 2)
+        out.update(_group_keys("corr_group", stats))
         if partial:
-            out["pcorr_group_mean"], out["pcorr_group_sd"] = torch.cat(pgstats[0], 1), torch.cat(pgstats[1], 1)
-            out["pcorr_group_quantiles"] = torch.cat(pgstats[2], 2)
+            out.update(_group_keys("pcorr_group", pstats))
         if keep_samples:
             out["corr_group_samples"] = Gb
             if partial:
                 out["pcorr_group_samples"] = PGb
     return out
-
-
-def _pop_sd(sq_mean, mean):
-    return torch.sqrt(torch.clamp(sq_mean - mean * mean, min=0.0))
 
 
 def summarize_Y(model, X_list, Y_list=None, n_sample=1000, index=None, quantiles=(0.025, 0.975), noise_tape=None,
@@ -677,12 +700,7 @@ def summarize_Y(model, X_list, Y_list=None, n_sample=1000, index=None, quantiles
     noise layout and stream as sample_Y; each chunk's tail is one fused call (csrc/ysum.hip) that reads only the
     I_n + 1 pairs of row n, so O(S N + N D) is stored and the (S, D, D, N) tensor of sample_Y is not.
     keep_samples=True adds Ys, Fs and tilde_ells, each (S, N)."""
-    qs = [float(q) for q in quantiles]
-    if any(not 0.0 <= q <= 1.0 for q in qs):
-        raise ValueError("quantiles must lie in [0, 1]")
-    n_sample = int(n_sample)
-    if n_sample < 1:
-        raise ValueError("n_sample must be at least 1")
+    qs, n_sample = _check_sampling_args(quantiles, n_sample)
     D = model.D
     ids = list(range(len(X_list))) if index is None else [int(j) for j in index]
     if len(ids) != len(X_list):
@@ -697,13 +715,10 @@ def summarize_Y(model, X_list, Y_list=None, n_sample=1000, index=None, quantiles
         if len(ys) != len(xs) or any(y.shape[0] != n for y, n in zip(ys, sizes)):
             raise ValueError("Y_list must match X_list entry by entry")
     dev = model.device_
-    I = torch.cat([torch.full((n,), j, dtype=torch.long) for n, j in zip(sizes, ids)]).to(dev)
-    x = torch.cat(xs).to(dev).reshape(-1, 1).contiguous()
+    x, I = prepare_inputs(model, xs, ids)
     st = _sampling_setup(model, x)
     N, M = st["N"], st["M"]
-    Q = len(st["pairs"])
-    per = M + N + Q * N + D * N + N
-    draws = _Draws(dev, noise_tape)
+    per, o_p, _, o_f = _noise_layout(st, False)
     sd_err = (st["s2_err"] + JIT) ** 0.5
     z = lambda *shape: torch.zeros(*shape, dtype=F64, device=dev)
     Ts, Ys, Fs = (torch.empty(n_sample, N, dtype=F64, device=dev) for _ in range(3))
@@ -714,16 +729,12 @@ def summarize_Y(model, X_list, Y_list=None, n_sample=1000, index=None, quantiles
         lse_max, lse_sum = torch.full((N,), float("-inf"), dtype=F64, device=dev), z(N)
     chunk = _chunk_size(n_sample, N, M)
     ws = H.y_workspace(D, N, chunk, dev)
-    done = 0
-    while done < n_sample:
-        S = min(chunk, n_sample - done)
-        zc = draws.take(S, per)
-        T, G, o_p, o_f = _sample_TG(st, zc)
+    for done, S, zc in _chunks(_Draws(dev, noise_tape), n_sample, chunk, per):
+        T, G, _, _ = _sample_TG(st, zc)
         Ts[done:done + S] = T
         H.y_accum_(st["pair_mu"], st["pair_sd"], G.contiguous(), zc[:, o_p:], zc[:, o_f:], I, sd_err,
                    Ys[done:done + S], Fs[done:done + S], F_sum, F_sq, L_sum, L_sq, G_sum, G_sq, y=y,
                    lse_max=lse_max, lse_sum=lse_sum, ws=ws)
-        done += S
     Y_mean, F_mean, L_mean, G_mean = Ys.mean(0), F_sum / n_sample, L_sum / n_sample, G_sum / n_sample
     Yq = _quantiles_dim0(Ys, qs)
     out = {"Y_mean": Y_mean, "Y_sd": _pop_sd((Ys * Ys).mean(0), Y_mean), "Y_quantiles": Yq,
@@ -733,8 +744,7 @@ def summarize_Y(model, X_list, Y_list=None, n_sample=1000, index=None, quantiles
            "G_mean": G_mean, "G_sd": _pop_sd(G_sq / n_sample, G_mean)}
     if y is not None:
         ok = torch.isfinite(y)
-        nan = torch.full((), float("nan"), dtype=F64, device=dev)
-        lpd = torch.where(ok, lse_max + torch.log(lse_sum) - float(np.log(n_sample)), nan)
+        lpd = _lpd(lse_max, lse_sum, ok, n_sample)
 
         def mean_of(v, mask):
             return torch.where(mask, v, torch.zeros_like(v)).sum() / mask.sum()          # 0 / 0 = NaN: none scored
@@ -779,12 +789,7 @@ def observed_grid(X_list, Y_list, x):
 
 def _impute_args(D, Y_obs, Y_true, n_sample, quantiles, N=None):
     """Validation of impute_Y that needs no device -> (Y_obs, Y_true as float64 numpy, n_sample, quantiles)."""
-    qs = [float(q) for q in quantiles]
-    if any(not 0.0 <= q <= 1.0 for q in qs):
-        raise ValueError("quantiles must lie in [0, 1]")
-    n_sample = int(n_sample)
-    if n_sample < 1:
-        raise ValueError("n_sample must be at least 1")
+    qs, n_sample = _check_sampling_args(quantiles, n_sample)
     Y_obs = np.asarray(Y_obs.detach().cpu() if torch.is_tensor(Y_obs) else Y_obs, np.float64)
     if Y_obs.ndim != 2 or Y_obs.shape[1] != D or (N is not None and Y_obs.shape[0] != N):
         raise ValueError(f"Y_obs must be (N, D) = ({'N' if N is None else N}, {D}), got {Y_obs.shape}")
@@ -836,9 +841,7 @@ def impute_Y(model, x, Y_obs, Y_true=None, n_sample=1000, quantiles=(0.025, 0.97
         raise ValueError(f"Y_obs must be (N, D) = ({x.shape[0]}, {model.D}), got {Y_obs.shape}")
     st = _sampling_setup(model, x)
     N, D, M = st["N"], st["D"], st["M"]
-    Q = len(st["pairs"])
-    per = M + N + Q * N + D * N + N * D
-    draws = _Draws(dev, noise_tape)
+    per = _noise_layout(st, True)[0]
     s2 = st["s2_err"] + JIT
     Yo = torch.from_numpy(np.ascontiguousarray(Y_obs)).to(dev)
     e_off, missing = H.missing_table(Yo)
@@ -859,10 +862,7 @@ def impute_Y(model, x, Y_obs, Y_true=None, n_sample=1000, quantiles=(0.025, 0.97
         lse_max, lse_sum = torch.full((E,), float("-inf"), dtype=F64, device=dev), z(E)
     chunk = _chunk_size(n_sample, N, M)
     ws = H.ycond_workspace(D, N, chunk, dev) if E > 0 else None
-    done = 0
-    while done < n_sample:
-        S = min(chunk, n_sample - done)
-        zc = draws.take(S, per)
+    for done, S, zc in _chunks(_Draws(dev, noise_tape), n_sample, chunk, per):
         T, mu_g, var_g, o_p, o_g, o_f = _sample_T_moments(st, zc)
         T_sum += T.sum(0)
         if Ts is not None:
@@ -874,7 +874,6 @@ def impute_Y(model, x, Y_obs, Y_true=None, n_sample=1000, quantiles=(0.025, 0.97
             if qs:
                 z_f = zc[:, o_f:].index_select(1, flat)
                 Yd[done:done + S] = Mu[done:done + S] + torch.sqrt(Var[done:done + S]) * z_f
-        done += S
     mean = mu_sum / n_sample
     filled = Yo.clone()
     filled.reshape(-1)[flat] = mean
@@ -887,8 +886,7 @@ def impute_Y(model, x, Y_obs, Y_true=None, n_sample=1000, quantiles=(0.025, 0.97
         out["quantiles"] = Yq
     if y is not None:
         ok = torch.isfinite(y)
-        nan = torch.full((), float("nan"), dtype=F64, device=dev)
-        lpd = torch.where(ok, lse_max + torch.log(lse_sum) - float(np.log(n_sample)), nan)
+        lpd = _lpd(lse_max, lse_sum, ok, n_sample)
         okf = ok.to(F64)
         d_of = missing[:, 1]
 

@@ -130,6 +130,26 @@ def test_kernel_matches_host_reference(D, N, S):
     _check(_run(inp, groups), corr, groups, D, f"corr groups D={D} N={N} S={S}")
 
 
+@pytest.mark.parametrize("D,N", [(17, 5), (128, 3)])
+def test_group_of_one_pair_is_the_correlation_fy_accumulates(D, N):
+    """cgroup.hip forms the normalised correlation as fy.hip does (loader and row sums shared in csrc/fy_tiles.hpp,
+    the tile product a copy of fy.hip's), so a group of one pair is bit for bit what fy.hip accumulates.  At S = 1 the samples are never sliced and fy_accum_ onto zeroed
+    sums leaves the sample's own correlation there.  The two-tile and the eight-tile instantiation, the latter with
+    its single wave per SIMD in cgroup.hip."""
+    from collaborative_nonstationary_multivariate_gaussian_process_amd import hip_ops as H
+    inp = GR.case(D, N, 1)[0]
+    pairs = [(i, j) for i in range(D) for j in range(i + 1)]
+    C = _run(inp, [[p] for p in pairs])                                   # (Q, N, 1)
+    pm, ps, z_p = _inputs(inp, 0, 1, False)
+    z = lambda *shape: torch.zeros(*shape, dtype=F64, device=_dev())
+    csum, csq = z(N, D, D), z(N, D, D)
+    H.fy_accum_(pm, ps, z(1, D, N), z_p, z(1, N * D), 0.0, z(1, N, D), csum, csq)
+    torch.cuda.synchronize()
+    ii, jj = (list(v) for v in zip(*pairs))
+    assert torch.equal(csum[:, ii, jj], C[:, :, 0].t())
+    assert torch.equal(csum[:, jj, ii], C[:, :, 0].t())                   # fy.hip writes both triangles
+
+
 @pytest.mark.parametrize("D,N,S", SHAPES)
 def test_pcorr_groups_match_host_reference(D, N, S):
     inp, _, pc, e64 = GR.case(D, N, S)
