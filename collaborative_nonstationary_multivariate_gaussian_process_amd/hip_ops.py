@@ -1370,6 +1370,44 @@ def corr_group_(pair_mu, pair_sd, z_p, goff, gent, C, s_off=0):
     return C
 
 
+def spectrum_workspace(D, N, S, k, device):
+    """Workspace of corr_spectrum_ with loadings for chunks of up to S samples (the slices' loading sums), or None
+    when the samples are not sliced (N >= 256 or S == 1)."""
+    return _slice_workspace(lambda d, n, s: L.lib().nmgp_corr_spectrum_workspace_bytes(d, n, s, int(k)), D, N, S,
+                            device)
+
+
+def corr_spectrum_(pair_mu, pair_sd, z_p, k, E, unconverged, s_off=0, load2_sum=None, ws=None):
+    """One chunk of per-sample eigenvalues of the output correlation matrix (csrc/spectrum.hip): E[r, n, s_off + s]
+    is the r-th largest eigenvalue for r < k, E[k, n, s_off + s] the effective dimension D^2 / sum lambda^2, written
+    for the S samples of z_p; nothing of E is accumulated.  pair_mu / pair_sd (Q, N) may have a row stride; z_p
+    (S, >= Q N) is a column range of a noise block (unit column stride); E (k + 1, N, ld_e) contiguous with
+    ld_e >= s_off + S; unconverged a 1-element int32 device tensor that counts the finite inputs whose sweeps ran out
+    (added to, never reset).  load2_sum (N, k, D) is accumulated onto: the squared loadings of the top k modes,
+    summed over the samples.  ws: spectrum_workspace(...) kept by a caller that runs several chunks, else allocated
+    here."""
+    Q, N, D, S, z_stride = _pair_args(pair_mu, pair_sd, z_p)
+    k, s_off = int(k), int(s_off)
+    assert 1 <= k <= D, "k"
+    L.require_device(E, "E")
+    assert E.dtype == torch.float64 and E.dim() == 3 and E.shape[:2] == (k + 1, N) and E.is_contiguous(), "E"
+    assert 0 <= s_off and s_off + S <= E.shape[2]
+    L.require_device(unconverged, "unconverged")
+    assert unconverged.dtype == torch.int32 and unconverged.numel() == 1, "unconverged"
+    lib = L.lib()
+    need = 0
+    if load2_sum is not None:
+        L.require_device(load2_sum, "load2_sum")
+        assert load2_sum.dtype == torch.float64 and load2_sum.shape == (N, k, D) and load2_sum.is_contiguous()
+        need = lib.nmgp_corr_spectrum_workspace_bytes(D, N, S, k)
+    ws = _ws_or_alloc(ws, need, z_p.device)
+    L.check(lib.nmgp_corr_spectrum_f64(L.ptr(pair_mu), L.ptr(pair_sd), pair_mu.stride(0), L.ptr(z_p), int(z_stride),
+                                       D, N, S, k, L.ptr(E), E.shape[2], s_off, L.ptr(load2_sum),
+                                       L.ptr(ws) if need > 0 else None, need, L.ptr(unconverged), L.stream_handle()),
+            "corr_spectrum")
+    return E
+
+
 def quantile_rows_max_S():
     """The longest row quantile_rows sorts (one workgroup's LDS)."""
     return int(L.lib().nmgp_quantile_rows_max_S())

@@ -1044,7 +1044,7 @@ def sample_FY(model, x, n_sample=1000):
 
 
 def summarize_FY(model, x, n_sample=1000, quantiles=(0.025, 0.975), corr_pairs=None, partial=False,
-                 corr_groups=None):
+                 corr_groups=None, spectrum=None):
     """What the reference's drivers make of sample_FY (NMGP_ECoG_full.py:329-332): means and quantile bands of
     tilde_ell and Y, mean and sd of the output correlations -- a dict of numpy arrays (predict.summarize_FY; the
     (S, N, D, D) correlation samples are never stored).  corr_pairs ("all" or a sequence of (i, j)) adds
@@ -1054,10 +1054,14 @@ def summarize_FY(model, x, n_sample=1000, quantiles=(0.025, 0.975), corr_pairs=N
     (len(quantiles), N, P).  corr_groups (a sequence of K groups of (i, j) pairs, e.g. from
     predict.groups_from_labels) adds the bands of the group-mean correlations the ECoG driver plots
     (NMGP_ECoG_full.py:456-544): "corr_group_sizes" (K,), "corr_group_mean" and "corr_group_sd" (N, K),
-    "corr_group_quantiles" (len(quantiles), N, K), and with partial=True the same three keys with "pcorr_group_"."""
+    "corr_group_quantiles" (len(quantiles), N, K), and with partial=True the same three keys with "pcorr_group_".
+    spectrum (an int k, 1 <= k <= D, or "all") adds the eigenvalue bands of the samples' correlation matrices:
+    "eig_mean" / "eig_sd" (N, k) and "eig_quantiles" (len(quantiles), N, k) of the k largest eigenvalues,
+    "eff_dim_mean" / "eff_dim_sd" (N,) and "eff_dim_quantiles" (len(quantiles), N) of the effective dimension
+    D^2 / sum lambda^2, "eig_loading2_mean" (N, k, D) and "spectrum_unconverged" (predict.summarize_FY)."""
     from . import predict
     out = predict.summarize_FY(model, torch.from_numpy(np.asarray(x)).to(F64), n_sample=n_sample, quantiles=quantiles,
-                               corr_pairs=corr_pairs, partial=partial, corr_groups=corr_groups)
+                               corr_pairs=corr_pairs, partial=partial, corr_groups=corr_groups, spectrum=spectrum)
     return {k: v.cpu().numpy() for k, v in out.items()}
 
 

@@ -431,6 +431,20 @@ def _parse_corr_groups(corr_groups, D):
     return lst
 
 
+def _parse_spectrum(spectrum, D):
+    """spectrum of summarize_FY -> k: "all" is D, else a plain int with 1 <= k <= D (a bool is refused); ValueError
+    for anything else."""
+    if isinstance(spectrum, str):
+        if spectrum != "all":
+            raise ValueError('spectrum: the only string accepted is "all"')
+        return D
+    if isinstance(spectrum, bool) or not isinstance(spectrum, (int, np.integer)):
+        raise ValueError('spectrum must be None, "all" or an int k with 1 <= k <= D')
+    if not 1 <= int(spectrum) <= D:
+        raise ValueError(f"spectrum: k must lie in 1..{D}")
+    return int(spectrum)
+
+
 def groups_from_labels(labels, between=True):
     """Within- and between-network groups for summarize_FY(corr_groups=...) from one hashable label per output ->
     (groups, names).  For every label a with at least two members, in order of first appearance: the group of all
@@ -552,7 +566,7 @@ def _group_keys(prefix, stats):
 
 
 def summarize_FY(model, x, n_sample=1000, quantiles=(0.025, 0.975), noise_tape=None, keep_samples=False,
-                 corr_pairs=None, band_bytes=1 << 30, partial=False, corr_groups=None):
+                 corr_pairs=None, band_bytes=1 << 30, partial=False, corr_groups=None, spectrum=None):
     """What the reference's drivers keep of NMGP.sample_FY (code/nmgp_dsvi.py:492-580; NMGP_ECoG_full.py:329-332):
     means and quantile bands of tilde_ell and Y, mean and population sd of the output correlations, as a dict of
     device tensors.  Same setup, chunking, noise layout and stream as sample_FY; each chunk's tail (pair samples,
@@ -597,10 +611,29 @@ def summarize_FY(model, x, n_sample=1000, quantiles=(0.025, 0.975), noise_tape=N
     independently of the pair batches: the first rides along with the summary's chunks, every further batch walks
     the noise stream again and launches only the group kernels.  The result does not depend on band_bytes.  With
     keep_samples=True the buffer is the full (K, N, S), whatever band_bytes says.  Anything else than None or such
-    a sequence raises ValueError before any device work; with None nothing is launched or returned."""
+    a sequence raises ValueError before any device work; with None nothing is launched or returned.
+
+    spectrum (a plain int k with 1 <= k <= D, or "all" for k = D) adds the eigenvalues of every sample's correlation
+    matrix at every input: how many independent modes the outputs have at x and how strong the common mode is.  The
+    matrix has trace D, so lambda / D is a mode's share.  Keys: "eig_mean" and "eig_sd" (N, k; mean and population
+    sd over the samples of the r-th largest eigenvalue), "eig_quantiles" (len(quantiles), N, k; exact, sorted like
+    the pair bands), "eff_dim_mean" / "eff_dim_sd" (N,) and "eff_dim_quantiles" (len(quantiles), N) of the effective
+    dimension (participation ratio) D^2 / sum_j lambda_j^2 over all D eigenvalues, "eig_loading2_mean" (N, k, D), the
+    mean over the samples of the squared loading u_rd^2 of output d on mode r (sign-free, each mode's sums to 1), and
+    "spectrum_unconverged", a 0-d int tensor counting the finite (sample, input) whose solve ran out of sweeps (0 on
+    everything tested); with keep_samples=True also "eig_samples" (k, N, S) and "eff_dim_samples" (N, S).  The mean
+    of the samples' eigenvalues is not the eigenvalues of corr_mean.  Modes are identified by rank, so two modes
+    whose eigenvalues cross over x swap labels there (and their loadings with them).  A sample whose L has a zero or
+    non-finite diagonal entry at an input (or that did not converge) is NaN in every eigenvalue and the effective
+    dimension at that input, and then so are that input's means, sds, quantiles and loadings.  Each chunk is one
+    more fused launch (csrc/spectrum.hip: one-sided Jacobi on diag(Is) L inside one workgroup's LDS), no second
+    walk of the noise stream and no (S, N, D, D) tensor.  The sample buffer is the full 8 (k + 1) S N bytes and is
+    not batched by band_bytes: a further batch would repeat the whole solve.  Anything else raises ValueError before
+    any device work; with None nothing is launched or returned."""
     qs, n_sample = _check_sampling_args(quantiles, n_sample)
     pairs_t = None if corr_pairs is None else _parse_corr_pairs(corr_pairs, model.D)
     groups = None if corr_groups is None else _parse_corr_groups(corr_groups, model.D)
+    kspec = 0 if spectrum is None else _parse_spectrum(spectrum, model.D)
     dev = model.device_
     x = torch.as_tensor(x).reshape(-1, 1).to(F64).to(dev).contiguous()
     st = _sampling_setup(model, x)
@@ -637,6 +670,11 @@ def summarize_FY(model, x, n_sample=1000, quantiles=(0.025, 0.975), noise_tape=N
         Gb = torch.empty(gb, N, n_sample, dtype=F64, device=dev)
         if partial:
             PGb = torch.empty(gb, N, n_sample, dtype=F64, device=dev)
+    if kspec:
+        Eb = torch.empty(kspec + 1, N, n_sample, dtype=F64, device=dev)  # the top k eigenvalues, then eff_dim
+        l2sum = torch.zeros(N, kspec, D, dtype=F64, device=dev)
+        unconv = torch.zeros(1, dtype=torch.int32, device=dev)
+        sws = H.spectrum_workspace(D, N, chunk, kspec, dev)
     # ---- the main pass: the sampling head and the fused tails of every chunk, the first batches riding along
     for done, S, zc in _chunks(draws, n_sample, chunk, per):
         T, G, _, _ = _sample_TG(st, zc)
@@ -653,6 +691,9 @@ def summarize_FY(model, x, n_sample=1000, quantiles=(0.025, 0.975), noise_tape=N
             if K:
                 kw.update(goff=tabs[0][0], gent=tabs[0][1], Cg=PGb, sg_off=done)
             H.pcorr_accum_(st["pair_mu"], st["pair_sd"], zc[:, o_p:], psum, psq, ws=pws, **kw)
+        if kspec:
+            H.corr_spectrum_(st["pair_mu"], st["pair_sd"], zc[:, o_p:], kspec, Eb, unconv, s_off=done,
+                             load2_sum=l2sum, ws=sws)
     mean = csum / n_sample
     out = {"tilde_ell_mean": Ts.mean(0), "tilde_ell_quantiles": _quantiles_dim0(Ts, qs),
            "Y_mean": Ys.mean(0), "Y_quantiles": _quantiles_dim0(Ys, qs),
@@ -686,6 +727,16 @@ def summarize_FY(model, x, n_sample=1000, quantiles=(0.025, 0.975), noise_tape=N
             out["corr_group_samples"] = Gb
             if partial:
                 out["pcorr_group_samples"] = PGb
+    # ---- the eigenvalue bands: rows 0..k-1 of the buffer are the eigenvalues, row k the effective dimension
+    if kspec:
+        G = T = zc = None
+        em, es, eq = _group_stats(Eb, qs)
+        out["eig_mean"], out["eig_sd"], out["eig_quantiles"] = em[:, :kspec], es[:, :kspec], eq[:, :, :kspec]
+        out["eff_dim_mean"], out["eff_dim_sd"], out["eff_dim_quantiles"] = em[:, kspec], es[:, kspec], eq[:, :, kspec]
+        out["eig_loading2_mean"] = l2sum / n_sample
+        out["spectrum_unconverged"] = unconv[0]
+        if keep_samples:
+            out["eig_samples"], out["eff_dim_samples"] = Eb[:kspec], Eb[kspec]
     return out
 
 

@@ -848,6 +848,40 @@ int nmgp_ycond_accum_f64(const double* pair_mu, const double* pair_sd, int64_t l
                          double* f2_sum, const double* y_true, double* lse_max, double* lse_sum, double* Mu,
                          double* Var, int64_t ld, int64_t s_off, void* ws, int64_t ws_bytes, hipStream_t stream);
 
+/* Eigenvalues of the sample's output correlation matrix, per posterior sample and input, fused (csrc/spectrum.hip):
+ * how many independent modes the outputs have and how strong the common mode is.  The reference has no such code;
+ * the quantity is a function of NMGP.sample_FY's correlation (code/nmgp_dsvi.py:567-569).  fp64.  For every sample
+ * s < S and input n < N, with L built from the pair samples exactly as in nmgp_fy_accum_f64 and
+ * Is_i = sqrt(1 / |row i of L|^2) as in nmgp_corr_group_f64:  G = diag(Is) L,  R = G G^T (trace D), and
+ * lambda_1 >= ... >= lambda_D the eigenvalues of R, found by one-sided Jacobi rotations of the column pairs of G in
+ * one workgroup's LDS (136 KiB at D = 128) until every pair has |g_p . g_q| <= sqrt(max(D, 4)) 2^-53 |g_p| |g_q|
+ * (LAPACK's dgesvj criterion; 2^-52 up to D = 4 -- at 2^-52 for every D about one random matrix in 50000 cycles
+ * between two roundings and never ends), at most 30 sweeps;
+ * then lambda_j = |g_j|^2 and u_j = g_j / |g_j|, sorted descending (ties by column).  Where not a single pair
+ * needed a rotation R is the identity (the diagonal of a correlation is exactly 1 in this family) and every
+ * lambda is exactly 1; so it is for D = 1.
+ *   E[(r * N + n) * ld_e + s_off + s] = lambda_{r+1} for r < k,
+ *   E[(k * N + n) * ld_e + s_off + s] = D^2 / sum_{j <= D} lambda_j^2   (the effective dimension, over all D),
+ *   with load2_sum (N, k, D contiguous; NULL = none): load2_sum[(n * k + r) * D + d] += u_{r+1,d}^2  (ACCUMULATED:
+ *   the caller zeroes it; sign-free, each mode's D values sum to 1).
+ * E is WRITTEN, every addressed element once, the other columns of a wider E left alone.  If some L_ii of the sample
+ * at n is 0, inf or NaN (or an Is is not finite and positive), every row of E at (s, n) is NaN and NaN is added to
+ * the loadings of n; other inputs and samples are not affected.  A finite input that has not converged after 30
+ * sweeps is NaN in the same way and adds 1 to *unconverged (device int32, required, never reset here).  E comes from
+ * the one workgroup that owns (s, n), from that sample alone: no floating-point atomics, the same bits in every run
+ * and however the samples are split over calls (s_off) or slices.  The samples are cut into slices by the rule of
+ * nmgp_fy_accum_f64 (none when N >= 256); the slices' loading sums go through `ws`
+ * (nmgp_corr_spectrum_workspace_bytes, 0 when unsliced or without loadings) and are added to load2_sum in slice
+ * order.  All indexing is 64-bit.  Returns 0 (nothing launched when N == 0 or S == 0), NMGP_ERR_SPECTRUM_ARG before
+ * any launch when D is outside 1..128, k outside 1..D, N, S, s_off or ws_bytes is negative, pair_mu, pair_sd, z_p,
+ * E or unconverged is NULL, ld_pair < N, z_stride < 0, ld_e < s_off + S, or load2_sum is given, the samples are
+ * sliced and the workspace is missing / too small.                                                              */
+#define NMGP_ERR_SPECTRUM_ARG (-66)
+int64_t nmgp_corr_spectrum_workspace_bytes(int D, int N, int S, int k);
+int nmgp_corr_spectrum_f64(const double* pair_mu, const double* pair_sd, int64_t ld_pair, const double* z_p,
+                           int64_t z_stride, int D, int N, int S, int k, double* E, int64_t ld_e, int64_t s_off,
+                           double* load2_sum, void* ws, int64_t ws_bytes, int32_t* unconverged, hipStream_t stream);
+
 /* Whole-step HIP graphs (the reference runs its step eagerly, code/nmgp_dsvi.py:829-854; the build captures
  * noise -> forward -> backward -> Adam once and replays it).  Capture goes straight through the HIP runtime:
  * begin on `stream` (thread-local mode; other streams join through event waits and must join back before
