@@ -9,6 +9,7 @@ import pytest
 import torch
 
 from oracle import nmgp_oracle as O
+from tests import _engine_cases as EC
 from tests import _golden as G
 from tests import dsvi_mirror as MR
 
@@ -31,10 +32,7 @@ CASES = {
 SURVEY_FP64_LOSS, SURVEY_FP64_GRAD = 1e-10, 1e-8
 
 
-def _rel(a, b):
-    a = torch.as_tensor(a).detach().double().cpu().reshape(-1)
-    b = torch.as_tensor(b).detach().double().cpu().reshape(-1)
-    return float((a - b).norm() / max(float(b.norm()), 1e-300))
+_rel = EC.rel
 
 
 def _setup(case):
@@ -53,13 +51,7 @@ def _setup(case):
     return g, xs, ys, p, eng, theta, grad
 
 
-def _unflatten(eng, flat):
-    out = {}
-    for k in O.PARAM_NAMES:
-        o, shp = eng.offs[k]
-        n = int(np.prod(shp)) if shp else 1
-        out[k] = flat[o:o + n].reshape(shp).cpu()
-    return out
+_unflatten = EC.unflatten
 
 
 @pytest.mark.parametrize("case", list(CASES))
@@ -94,28 +86,7 @@ def test_engine_intermediates_vs_mirror():
     x = torch.from_numpy(g["x"]); y = torch.from_numpy(g["y"]); z = torch.from_numpy(g["z"])
     loss, gr, it = MR.forward_backward({k: v.clone() for k, v in p.items()}, x, y, [int(s) for s in g["sizes"]], z,
                                        float(g["N"]), torch.from_numpy(g["noise"]))
-    D = eng.D
-    checks = {
-        "P_t": (eng.P[0], it["P"]["t"]), "P_0": (eng.P[1], it["P"]["0"]), "P_1": (eng.P[2], it["P"]["1"]),
-        "Ainv_t": (eng.Ainv[0], it["Ainv"]["t"]), "v": (eng.v, it["v"]), "ellX": (eng.ellX, it["ellX"]),
-        "K_G12": (eng.K12[3], it["KG12"]), "Ainv_G": (eng.Ainv[3], it["Ainv"]["G"]), "P_G": (eng.P[3], it["P"]["G"]),
-        "KL": (eng.facbuf[:eng.NF], torch.cat([it["KL"][:D], it["KL"][D + 1:], it["KL"][D:D + 1]])), "R_G": (eng.R[3], it["Rm"]["G"]), "R_0": (eng.R[1], it["Rm"]["0"]),
-        "R_t": (eng.R[0], it["Rm"]["t"]), "Abar_G": (eng.Abar[3], it["Abar"]["G"]), "Abar_0": (eng.Abar[1], it["Abar"]["0"]),
-        "Abar_t": (eng.Abar[0], it["Abar"]["t"]), "Pbar_G": (eng.Pbar[3], it["Pbar"]["G"]),
-        "Pbar_0": (eng.Pbar[1], it["Pbar"]["0"]), "Pbar_t": (eng.Pbar[0], it["Pbar"]["t"]),
-        "mbar": (eng.rowbuf[:D].t(), it["mbar"]), "sbar": (eng.rowbuf[D:2 * D].t(), it["sbar"]),
-        "vbar": (eng.vbar, None),
-    }
-    errs = {}
-    for k, (a, b) in checks.items():
-        if b is None:
-            continue
-        errs[k] = _rel(a, b)
-    gd = _unflatten(eng, grad)
-    for k in O.PARAM_NAMES:
-        if float(gr[k].norm()) > 0:
-            errs["grad_" + k] = _rel(gd[k], gr[k])
-    errs["loss"] = abs(float(eng.out[0]) - float(loss)) / abs(float(loss))
+    errs = EC.intermediate_errs(eng, grad, loss, gr, it)
     bad = {k: e for k, e in errs.items() if not e < 1e-7}
     assert not bad, f"mismatching intermediates {bad}; all {errs}"
 
