@@ -1904,11 +1904,7 @@ static size_t chol_tp_smem(int n) {
 
 template <int NTPW1, int NTPWU>
 static void chol_tp_go(const TpDev& a, unsigned grid, size_t sm, hipStream_t s) {
-  static std::once_flag once;
-  std::call_once(once, [] {
-    (void)hipFuncSetAttribute((const void*)chol_tp_kernel<NTPW1, NTPWU>, hipFuncAttributeMaxDynamicSharedMemorySize,
-                              160 * 1024);
-  });
+  allow_dynamic_lds<chol_tp_kernel<NTPW1, NTPWU>>(160 * 1024);
   hipLaunchKernelGGL((chol_tp_kernel<NTPW1, NTPWU>), dim3(grid), dim3(RW * 64), sm, s, a);
 }
 
@@ -1954,7 +1950,9 @@ static int chol_tp_launch(const nmgp_chol_tp_args* h, hipStream_t s) {
     if (a.rows[m]) a.tpm[a.ntp++] = m;
   }
   a.nct = g.B > 0 ? (int)((g.B + TPR - 1) / TPR) : 0;
-  a.dbg = getenv("NMGP_TP_DBG") ? atoi(getenv("NMGP_TP_DBG")) : 0;
+  // (diagnostics of tools/chol_tp_probe.py and nmgp_chol_tp_trace; read once per process)
+  static const int dbg = [] { const char* e = getenv("NMGP_TP_DBG"); return e ? atoi(e) : 0; }();
+  a.dbg = dbg;
   if (g.vg_wgs < 0 || g.vg_wgs > 64) return -1;
   if (g.vg_wgs > 0) {
     if (!g.vg_muv || !g.vg_z || !g.vg_v || !g.vg_ellZ || !g.vg_K22 || !g.Z || a.rows[0] != 0) return -1;
@@ -2015,11 +2013,7 @@ static int potrf_launch(T* A, int64_t n, int64_t lda, int64_t strideA, int64_t b
   if (n == 0 || batch == 0) return NMGP_OK;
   const size_t sm = potrf_smem<T>((int)n);
   if (sm > 160 * 1024) return -2;
-  static bool attr_done = false;
-  if (!attr_done) {
-    (void)hipFuncSetAttribute((const void*)potrf_kernel<T>, hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024);
-    attr_done = true;
-  }
+  allow_dynamic_lds<potrf_kernel<T>>(160 * 1024);
   hipLaunchKernelGGL(potrf_kernel<T>, dim3((unsigned)batch), dim3(CT), sm, s, A, (int)n, lda, strideA, info);
   NMGP_CHECK_LAUNCH();
   return NMGP_OK;
@@ -2037,79 +2031,29 @@ static int trtri_launch(const T* L, int64_t n, int64_t ldl, int64_t strideL, T* 
   if (n == 0 || batch == 0) return NMGP_OK;
   const size_t sm = trtri_smem<T>((int)n);
   if (sm > 160 * 1024) return -2;
-  static bool attr_done = false;
-  if (!attr_done) {
-    (void)hipFuncSetAttribute((const void*)trtri_kernel<T>, hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024);
-    attr_done = true;
-  }
+  allow_dynamic_lds<trtri_kernel<T>>(160 * 1024);
   hipLaunchKernelGGL(trtri_kernel<T>, dim3((unsigned)batch), dim3(CT), sm, s, L, (int)n, ldl, strideL, X, ldx,
                      strideX);
   NMGP_CHECK_LAUNCH();
   return NMGP_OK;
 }
 
-template <typename T, int NTPW>
+// One launch of a chol_inv kernel family over `batch` matrices, WGS workgroups (the family's roles) per matrix: the
+// fused register-resident kernel (1), the factor / inverse pair (2), the inverse over two workgroups (3) and the
+// separate update workgroup (4).
+template <auto Kernel, int WGS, typename T>
 static void chol_inv_go(T* A, int n, int64_t lda, int64_t sA, T* X, int64_t ldx, int64_t sX, int64_t batch,
                         int32_t* info, size_t sm, hipStream_t s, int col_off, int info_first) {
-  static bool attr_done = false;
-  if (!attr_done) {
-    (void)hipFuncSetAttribute((const void*)chol_inv_kernel<T, NTPW>, hipFuncAttributeMaxDynamicSharedMemorySize,
-                              160 * 1024);
-    attr_done = true;
-  }
-  hipLaunchKernelGGL((chol_inv_kernel<T, NTPW>), dim3((unsigned)batch), dim3(RW * 64), sm, s, A, n, lda, sA, X, ldx,
-                     sX, info, col_off, info_first);
-}
-
-// one diagonal block (n <= 256) with the fused register-resident kernel
-template <typename T, int NTPW>
-static void chol_inv2_go(T* A, int n, int64_t lda, int64_t sA, T* X, int64_t ldx, int64_t sX, int64_t batch,
-                         int32_t* info, size_t sm, hipStream_t s, int col_off, int info_first) {
-  static bool attr_done = false;
-  if (!attr_done) {
-    (void)hipFuncSetAttribute((const void*)chol_inv2_kernel<T, NTPW>, hipFuncAttributeMaxDynamicSharedMemorySize,
-                              160 * 1024);
-    attr_done = true;
-  }
-  hipLaunchKernelGGL((chol_inv2_kernel<T, NTPW>), dim3((unsigned)(2 * batch)), dim3(RW * 64), sm, s, A, n, lda, sA, X,
-                     ldx, sX, info, col_off, info_first);
+  allow_dynamic_lds<Kernel>(160 * 1024);
+  hipLaunchKernelGGL(Kernel, dim3((unsigned)(WGS * batch)), dim3(RW * 64), sm, s, A, n, lda, sA, X, ldx, sX, info,
+                     col_off, info_first);
 }
 
 // Two-role split pays from n = 32 up; its workgroup pairs must be co-resident, so a launch holds at
 // most 128 matrices (256 workgroups, one per CU).  The three-role split (inverse over two
 // workgroups) for up to 85 matrices.
 static bool use_two_role(int n, int64_t batch) { return n >= 32 && n <= 256 && batch <= 128; }
-static bool use_three_role(int n, int64_t batch) {
-  static int off = -1;
-  if (off < 0) off = getenv("NMGP_CHOL_TWO_ROLE") ? 1 : 0;
-  return !off && n >= 128 && n <= 256 && batch <= 85;
-}
-
-template <typename T, int NTPW, int NTPW1>
-static void chol_inv3_go(T* A, int n, int64_t lda, int64_t sA, T* X, int64_t ldx, int64_t sX, int64_t batch,
-                         int32_t* info, size_t sm, hipStream_t s, int col_off, int info_first) {
-  static bool attr_done = false;
-  if (!attr_done) {
-    (void)hipFuncSetAttribute((const void*)chol_inv3_kernel<T, NTPW, NTPW1>, hipFuncAttributeMaxDynamicSharedMemorySize,
-                              160 * 1024);
-    attr_done = true;
-  }
-  hipLaunchKernelGGL((chol_inv3_kernel<T, NTPW, NTPW1>), dim3((unsigned)(3 * batch)), dim3(RW * 64), sm, s, A, n, lda,
-                     sA, X, ldx, sX, info, col_off, info_first);
-}
-
-template <typename T, int NTPW1, int NTPWU>
-static void chol_inv7_go(T* A, int n, int64_t lda, int64_t sA, T* X, int64_t ldx, int64_t sX, int64_t batch,
-                         int32_t* info, size_t sm, hipStream_t s, int col_off, int info_first) {
-  static bool attr_done = false;
-  if (!attr_done) {
-    (void)hipFuncSetAttribute((const void*)chol_inv7_kernel<T, 1, NTPW1, NTPWU>,
-                              hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024);
-    attr_done = true;
-  }
-  hipLaunchKernelGGL((chol_inv7_kernel<T, 1, NTPW1, NTPWU>), dim3((unsigned)(4 * batch)), dim3(RW * 64), sm, s, A, n,
-                     lda, sA, X, ldx, sX, info, col_off, info_first);
-}
+static bool use_three_role(int n, int64_t batch) { return n >= 128 && n <= 256 && batch <= 85; }
 
 // Four-role kernel (separate update workgroup): the default from n = 192 (at n = 256 f64: 85-88 us against
 // the three-role kernel's 95-97 us per launch, PM2.5 step 1317-1320 -> 1339-1381 it/s in an A/B on the box;
@@ -2126,9 +2070,7 @@ static bool use_four_role(int n, int64_t batch) {
 // the multi-role kernels keep 64-bit control words in X's row 0: f32 needs them 8-byte aligned
 template <typename T> static bool chol_ctl_ok(int n, const T* X, int64_t sX) {
   if (sizeof(T) == 8) return true;
-  static int off = -1;
-  if (off < 0) off = getenv("NMGP_CHOL_F32_ROLES") && atoi(getenv("NMGP_CHOL_F32_ROLES")) == 0 ? 1 : 0;
-  return !off && n % 2 == 0 && ((uintptr_t)X % 8) == 0 && sX % 2 == 0;
+  return n % 2 == 0 && ((uintptr_t)X % 8) == 0 && sX % 2 == 0;
 }
 
 template <typename T>
@@ -2139,51 +2081,54 @@ static int chol_inv_small(T* A, int n, int64_t lda, int64_t sA, T* X, int64_t ld
   const size_t sm = chol_inv_smem<T>(n) > sm_min ? chol_inv_smem<T>(n) : sm_min;
   // multi-role kernels (f64 always; f32 when the control words can be 8-byte aligned, round 2)
   if (chol_ctl_ok<T>(n, X, sX)) {
-    if (two_role && use_four_role(n, batch) && !getenv("NMGP_CHOL_FUSED1")) {
+    if (two_role && use_four_role(n, batch)) {
       const size_t sm7 = sm + (size_t)(((n + 15) >> 4) * 16 * CP) * sizeof(T);   // + the third L buffer
       // inverse-role tiles as the three-role kernel's thresholds; update-role tiles: (nt-4)(nt-3)/2 <= RW*10
       if (ntiles <= RW * 5)
-        chol_inv7_go<T, 3, 2>(A, n, lda, sA, X, ldx, sX, batch, info, sm7, s, col_off, info_first);
+        chol_inv_go<chol_inv7_kernel<T, 1, 3, 2>, 4>(A, n, lda, sA, X, ldx, sX, batch, info, sm7, s, col_off,
+                                                     info_first);
       else if (ntiles <= RW * 9)
-        chol_inv7_go<T, 5, 4>(A, n, lda, sA, X, ldx, sX, batch, info, sm7, s, col_off, info_first);
+        chol_inv_go<chol_inv7_kernel<T, 1, 5, 4>, 4>(A, n, lda, sA, X, ldx, sX, batch, info, sm7, s, col_off,
+                                                     info_first);
       else
-        chol_inv7_go<T, 9, 10>(A, n, lda, sA, X, ldx, sX, batch, info, sm7, s, col_off, info_first);
+        chol_inv_go<chol_inv7_kernel<T, 1, 9, 10>, 4>(A, n, lda, sA, X, ldx, sX, batch, info, sm7, s, col_off,
+                                                      info_first);
       NMGP_CHECK_LAUNCH();
       return NMGP_OK;
     }
-    if (two_role && use_three_role(n, batch) && !getenv("NMGP_CHOL_FUSED1")) {
+    if (two_role && use_three_role(n, batch)) {
       if (ntiles <= RW * 5)
-        chol_inv3_go<T, 5, 3>(A, n, lda, sA, X, ldx, sX, batch, info, sm, s, col_off, info_first);
+        chol_inv_go<chol_inv3_kernel<T, 5, 3>, 3>(A, n, lda, sA, X, ldx, sX, batch, info, sm, s, col_off, info_first);
       else if (ntiles <= RW * 9)
-        chol_inv3_go<T, 9, 5>(A, n, lda, sA, X, ldx, sX, batch, info, sm, s, col_off, info_first);
+        chol_inv_go<chol_inv3_kernel<T, 9, 5>, 3>(A, n, lda, sA, X, ldx, sX, batch, info, sm, s, col_off, info_first);
       else
-        chol_inv3_go<T, 17, 9>(A, n, lda, sA, X, ldx, sX, batch, info, sm, s, col_off, info_first);
+        chol_inv_go<chol_inv3_kernel<T, 17, 9>, 3>(A, n, lda, sA, X, ldx, sX, batch, info, sm, s, col_off, info_first);
       NMGP_CHECK_LAUNCH();
       return NMGP_OK;
     }
-    if (two_role && use_two_role(n, batch) && !getenv("NMGP_CHOL_FUSED1")) {
+    if (two_role && use_two_role(n, batch)) {
       if (ntiles <= RW * 3)
-        chol_inv2_go<T, 3>(A, n, lda, sA, X, ldx, sX, batch, info, sm, s, col_off, info_first);
+        chol_inv_go<chol_inv2_kernel<T, 3>, 2>(A, n, lda, sA, X, ldx, sX, batch, info, sm, s, col_off, info_first);
       else if (ntiles <= RW * 5)
-        chol_inv2_go<T, 5>(A, n, lda, sA, X, ldx, sX, batch, info, sm, s, col_off, info_first);
+        chol_inv_go<chol_inv2_kernel<T, 5>, 2>(A, n, lda, sA, X, ldx, sX, batch, info, sm, s, col_off, info_first);
       else if (ntiles <= RW * 9)
-        chol_inv2_go<T, 9>(A, n, lda, sA, X, ldx, sX, batch, info, sm, s, col_off, info_first);
+        chol_inv_go<chol_inv2_kernel<T, 9>, 2>(A, n, lda, sA, X, ldx, sX, batch, info, sm, s, col_off, info_first);
       else
-        chol_inv2_go<T, 17>(A, n, lda, sA, X, ldx, sX, batch, info, sm, s, col_off, info_first);
+        chol_inv_go<chol_inv2_kernel<T, 17>, 2>(A, n, lda, sA, X, ldx, sX, batch, info, sm, s, col_off, info_first);
       NMGP_CHECK_LAUNCH();
       return NMGP_OK;
     }
   }
   if (ntiles <= RW * 1)
-    chol_inv_go<T, 1>(A, n, lda, sA, X, ldx, sX, batch, info, sm, s, col_off, info_first);
+    chol_inv_go<chol_inv_kernel<T, 1>, 1>(A, n, lda, sA, X, ldx, sX, batch, info, sm, s, col_off, info_first);
   else if (ntiles <= RW * 3)
-    chol_inv_go<T, 3>(A, n, lda, sA, X, ldx, sX, batch, info, sm, s, col_off, info_first);
+    chol_inv_go<chol_inv_kernel<T, 3>, 1>(A, n, lda, sA, X, ldx, sX, batch, info, sm, s, col_off, info_first);
   else if (ntiles <= RW * 5)
-    chol_inv_go<T, 5>(A, n, lda, sA, X, ldx, sX, batch, info, sm, s, col_off, info_first);
+    chol_inv_go<chol_inv_kernel<T, 5>, 1>(A, n, lda, sA, X, ldx, sX, batch, info, sm, s, col_off, info_first);
   else if (ntiles <= RW * 9)
-    chol_inv_go<T, 9>(A, n, lda, sA, X, ldx, sX, batch, info, sm, s, col_off, info_first);
+    chol_inv_go<chol_inv_kernel<T, 9>, 1>(A, n, lda, sA, X, ldx, sX, batch, info, sm, s, col_off, info_first);
   else
-    chol_inv_go<T, 17>(A, n, lda, sA, X, ldx, sX, batch, info, sm, s, col_off, info_first);
+    chol_inv_go<chol_inv_kernel<T, 17>, 1>(A, n, lda, sA, X, ldx, sX, batch, info, sm, s, col_off, info_first);
   NMGP_CHECK_LAUNCH();
   return NMGP_OK;
 }
@@ -2275,9 +2220,8 @@ static int chol_split_point(int n) {
 static int chol_inv_rec_big(float* A, int n, int64_t lda, int64_t sA, float* X, int64_t ldx, int64_t sX,
                             int64_t batch, int32_t* info, hipStream_t s, int col_off, void* ws, int full = 1) {
   // leaves up to 256 wide on the fused register-resident kernels (round 6: ECoG 0.2734 -> 0.2707 s, HCP 59.5 -> 60.1
-  // it/s against 128-wide leaves, profiles/r06zj_rec_leaf_ab.txt); NMGP_REC_LEAF=128 keeps the deeper recursion
-  static const int leaf = [] { const char* e = getenv("NMGP_REC_LEAF"); return e && atoi(e) == 128 ? 128 : 256; }();
-  if (n <= leaf) return chol_inv_small<float>(A, n, lda, sA, X, ldx, sX, batch, info, s, col_off, col_off == 0);
+  // it/s against 128-wide leaves, profiles/r06zj_rec_leaf_ab.txt)
+  if (n <= 256) return chol_inv_small<float>(A, n, lda, sA, X, ldx, sX, batch, info, s, col_off, col_off == 0);
   const int n1 = chol_split_point(n);
   const int n2 = n - n1, nb = (int)batch;
   int rc;

@@ -3,6 +3,8 @@
 #include <hip/hip_runtime.h>
 #include <stdint.h>
 
+#include <mutex>
+
 #include "../../include/nmgp_hip.h"
 
 #define NMGP_CHECK_LAUNCH()                                      \
@@ -16,6 +18,17 @@ constexpr int kWave = 64;
 
 // The caller's workspace (ws, ws_bytes) holds the `need` bytes that an entry point's size function asks for.
 inline bool ws_covers(int64_t need, const void* ws, int64_t ws_bytes) { return need <= 0 || (ws && ws_bytes >= need); }
+
+// Allow Kernel up to `bytes` of dynamic LDS (a launch above the default limit fails without it).  Host side, before the
+// launch: the attribute call is made once per kernel instantiation, by whichever thread launches it first, with that
+// call's `bytes` -- so pass the kernel's largest size (or a bound of it) every time.
+template <auto Kernel>
+inline void allow_dynamic_lds(size_t bytes) {
+  static std::once_flag once;
+  std::call_once(once, [bytes] {
+    (void)hipFuncSetAttribute((const void*)Kernel, hipFuncAttributeMaxDynamicSharedMemorySize, (int)bytes);
+  });
+}
 
 // Global-address-space pointer.  Pointers that arrive inside descriptor structs are generic, and
 // generic (flat) loads count against lgkmcnt as well as vmcnt: an LDS wait would then also wait

@@ -207,12 +207,7 @@ int nmgp_quantile_rows_f64(const double* C, int64_t rows, int S, int64_t ld, con
   const int64_t blocks = (rows + R - 1) / R;
   if (blocks > 0x7fffffffLL) return NMGP_ERR_CORRQ_ARG;
   const size_t smem = (size_t)R * P2 * sizeof(double);
-  static bool attr_done = false;
-  if (!attr_done) {
-    (void)hipFuncSetAttribute((const void*)quantile_rows_kernel, hipFuncAttributeMaxDynamicSharedMemorySize,
-                              (int)(kQrMaxS * sizeof(double)));
-    attr_done = true;
-  }
+  allow_dynamic_lds<quantile_rows_kernel>(kQrMaxS * sizeof(double));
   for (int q0 = 0; q0 < nq; q0 += kQrMaxQ) {
     QrQs h;
     const int cnt = nq - q0 < kQrMaxQ ? nq - q0 : kQrMaxQ;

@@ -1194,8 +1194,9 @@ __global__ __launch_bounds__(256) void adam_flat_kernel(T* th, const T* g, T* m,
   }
 }
 
-// the flat vector [0, n) with `ntri` ranges (offset, blocks) of lower-triangular M x M blocks: the dense kernel on
-// the gaps, the triangular one on the ranges, then the step counter
+// the flat vector [0, n) with `ntri` ranges (offset, blocks) of lower-triangular M x M blocks: one launch over the
+// whole vector where it takes the ranges (at most 4, ascending, 16-byte aligned); for the inputs it refuses the dense
+// kernel on the gaps and the triangular one on the ranges; then the step counter
 template <typename T>
 static int adam_lower(T* th, const T* g, T* m, T* v, int64_t n, const int64_t* tri, int ntri, int M, int64_t* step,
                       T lr, T b1, T b2, T eps, hipStream_t s, bool advanced = false) {
@@ -1203,8 +1204,7 @@ static int adam_lower(T* th, const T* g, T* m, T* v, int64_t n, const int64_t* t
   if (M <= 0) return -8;
   constexpr int V = 16 / (int)sizeof(T);
   const bool aligned = ((((uintptr_t)th) | ((uintptr_t)g) | ((uintptr_t)m) | ((uintptr_t)v)) & 15) == 0;
-  static const bool flat = [] { const char* e = getenv("NMGP_ADAM_FLAT"); return !e || atoi(e) != 0; }();
-  if ((flat || advanced) && aligned && ntri <= 4 && M % V == 0) {
+  if (aligned && ntri <= 4 && M % V == 0) {
     AdamTri tr{};
     tr.n = ntri;
     int64_t at = 0;

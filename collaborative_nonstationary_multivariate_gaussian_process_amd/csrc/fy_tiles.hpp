@@ -101,11 +101,7 @@ int fy_tri_reduce(const double* ws, int nsl, int D, int N, double* out_sum, doub
 // extent is the kernel's last parameter (fy_block_input).
 template <auto Kernel, class... Args>
 static int fy_launch(size_t smem, int N, int nsl, hipStream_t s, Args... args) {
-  static bool attr_done = false;
-  if (!attr_done) {
-    (void)hipFuncSetAttribute((const void*)Kernel, hipFuncAttributeMaxDynamicSharedMemorySize, (int)smem);
-    attr_done = true;
-  }
+  allow_dynamic_lds<Kernel>(smem);
   const int n_blocks = (N + kFyXcds - 1) / kFyXcds * kFyXcds;
   hipLaunchKernelGGL(Kernel, dim3((unsigned)n_blocks, (unsigned)nsl), dim3(kFyThreads), smem, s, args..., n_blocks);
   NMGP_CHECK_LAUNCH();

@@ -983,11 +983,7 @@ int potrf_step_f32(float* P, float* C, const float* X, int64_t lda, int n2, int 
   }
   // (a narrower last block: the 128-row tile form)
   const size_t lds = 2 * BSTAGE * sizeof(float);
-  static bool attr = false;
-  if (!attr) {
-    (void)hipFuncSetAttribute((const void*)potrf_step_kernel, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
-    attr = true;
-  }
+  allow_dynamic_lds<potrf_step_kernel>(lds);
   hipLaunchKernelGGL(potrf_step_kernel, dim3((unsigned)((n2 + BBM - 1) / BBM)), dim3(256), lds, s, pa);
   NMGP_CHECK_LAUNCH();
   return NMGP_OK;
@@ -1026,6 +1022,14 @@ struct BigEpi {
   const int32_t* rseg = nullptr; const int32_t* rspan = nullptr;
   float* D = nullptr; const int64_t* offD = nullptr; int64_t sDi = 0;
 };
+
+// one launch of a gemm_big_kernel instantiation (512 / NB threads, both LDS stages as dynamic LDS)
+template <bool AK, bool BK, int MODE, int NB>
+static void gemm_big_go(const BigGemmArgs& g, dim3 gd, hipStream_t s) {
+  constexpr size_t lds = 2 * BSTAGE * sizeof(float);
+  allow_dynamic_lds<gemm_big_kernel<AK, BK, MODE, NB>>(lds);
+  hipLaunchKernelGGL((gemm_big_kernel<AK, BK, MODE, NB>), gd, dim3(512 / NB), lds, s, g);
+}
 
 static int gemm_big_f32_ex(const float* A, int64_t lda, const float* B, int64_t ldb, int b_kcontig, float* C,
                            int64_t sCi, int64_t sCj, int m, int n, int k, int flags, float alpha, float beta,
@@ -1092,18 +1096,9 @@ static int gemm_big_f32_ex(const float* A, int64_t lda, const float* B, int64_t 
   g.persist = (!sk && S == 1 && batch > 1) ? 1 : 0;
   g.ws = (float*)ws;
   g.counters = ws ? (int32_t*)((char*)ws + (size_t)kBigSlots * BSLOT * sizeof(float)) : nullptr;
-  const size_t lds = 2 * BSTAGE * sizeof(float);
   const dim3 gd = g.persist ? dim3((unsigned)min((int64_t)P, total), 1u)
                              : dim3(sk ? (unsigned)P : (unsigned)(g.tiles * S), (unsigned)batch);
   const bool epi = flags & NMGP_EPI;
-  auto go = [&](auto kern, int nb) {
-    static bool attr = false;   // one per instantiation
-    if (!attr) {
-      (void)hipFuncSetAttribute((const void*)kern, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
-      attr = true;
-    }
-    hipLaunchKernelGGL(kern, gd, dim3(512 / nb), lds, s, g);
-  };
   const bool offs = offA != nullptr;
   if (offs && (offB == nullptr || offC == nullptr)) return -1;
   if (!offs && (diag_add != 0.0f || (flags & NMGP_OUT_TRIL))) return -1;   // those live in the offsets variants
@@ -1111,27 +1106,27 @@ static int gemm_big_f32_ex(const float* A, int64_t lda, const float* B, int64_t 
     // the KL L-bar forms: both operands transposed, or (the solve form's R = L21 - C21 W11) A k-contiguous
     if (!offs || g.b_kcontig) return -1;
     if (g.a_kcontig)
-      go(gemm_big_kernel<true, false, 2, 2>, 2);   // (8 waves: 88 bytes of scratch per lane)
+      gemm_big_go<true, false, 2, 2>(g, gd, s);   // (8 waves: 88 bytes of scratch per lane)
     else
-      go(gemm_big_kernel<false, false, 2, 2>, 2);
+      gemm_big_go<false, false, 2, 2>(g, gd, s);
   } else if (offs) {
     if (g.a_kcontig && g.b_kcontig)
-      go(gemm_big_kernel<true, true, 1, kBigNB>, kBigNB);
+      gemm_big_go<true, true, 1, kBigNB>(g, gd, s);
     else if (g.a_kcontig)
-      go(gemm_big_kernel<true, false, 1, kBigNB>, kBigNB);
+      gemm_big_go<true, false, 1, kBigNB>(g, gd, s);
     else if (g.b_kcontig)
-      go(gemm_big_kernel<false, true, 1, kBigNB>, kBigNB);
+      gemm_big_go<false, true, 1, kBigNB>(g, gd, s);
     else
-      go(gemm_big_kernel<false, false, 1, 2>, 2);
+      gemm_big_go<false, false, 1, 2>(g, gd, s);
   } else {
     if (g.a_kcontig && g.b_kcontig)
-      go(gemm_big_kernel<true, true, 0, kBigNB>, kBigNB);
+      gemm_big_go<true, true, 0, kBigNB>(g, gd, s);
     else if (g.a_kcontig)
-      go(gemm_big_kernel<true, false, 0, kBigNB>, kBigNB);
+      gemm_big_go<true, false, 0, kBigNB>(g, gd, s);
     else if (g.b_kcontig)
-      go(gemm_big_kernel<false, true, 0, kBigNB>, kBigNB);
+      gemm_big_go<false, true, 0, kBigNB>(g, gd, s);
     else
-      go(gemm_big_kernel<false, false, 0, 2>, 2);
+      gemm_big_go<false, false, 0, 2>(g, gd, s);
   }
   NMGP_CHECK_LAUNCH();
   return NMGP_OK;

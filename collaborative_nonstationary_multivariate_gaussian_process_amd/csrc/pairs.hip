@@ -369,12 +369,7 @@ static int pair_quad(const T* A, const T* L, T* C, const nmgp_pair_desc* descs, 
   if (rc) return rc;
   if (quad_smem<T>(M) > 160 * 1024) return -7;
   if (nprob == 0) return NMGP_OK;
-  static bool attr = false;
-  if (!attr) {
-    (void)hipFuncSetAttribute((const void*)pair_quad_kernel<T>, hipFuncAttributeMaxDynamicSharedMemorySize,
-                              160 * 1024);
-    attr = true;
-  }
+  allow_dynamic_lds<pair_quad_kernel<T>>(160 * 1024);
   const int ncb = (M + 64 * PairCfg<T>::V - 1) / (64 * PairCfg<T>::V);
   hipLaunchKernelGGL(pair_quad_kernel<T>, dim3((unsigned)nprob, (unsigned)ncb), dim3(PT), quad_smem<T>(M), s, A, L, C,
                      descs, seg, M);

@@ -267,13 +267,8 @@ __global__ void spectrum_reduce_kernel(const double* __restrict__ ws, int nsl, i
 
 template <int LS, class... Args>
 static int spectrum_launch(int D, int N, int nsl, hipStream_t s, Args... args) {
-  static bool attr_done = false;
-  if (!attr_done) {
-    constexpr int dmax = spec_max_d(LS);
-    (void)hipFuncSetAttribute((const void*)corr_spectrum_kernel<LS>, hipFuncAttributeMaxDynamicSharedMemorySize,
-                              dmax * spec_ld(dmax, LS) * (int)sizeof(double));
-    attr_done = true;
-  }
+  constexpr int dmax = spec_max_d(LS);
+  allow_dynamic_lds<corr_spectrum_kernel<LS>>(dmax * spec_ld(dmax, LS) * sizeof(double));
   const size_t smem = (size_t)D * spec_ld(D + (D & 1), LS) * sizeof(double);
   const int n_blocks = (N + kFyXcds - 1) / kFyXcds * kFyXcds;
   hipLaunchKernelGGL(corr_spectrum_kernel<LS>, dim3((unsigned)n_blocks, (unsigned)nsl), dim3(kFyThreads), smem, s,

@@ -81,9 +81,18 @@ def lower_block_ranges(offs):
 # the triangular-block Adam from this M on.  Round 6: nmgp_adam_lower is one launch over the whole flat vector
 # (csrc/dsvi.hip adam_flat_kernel), so the PM2.5 shape (M = 256) takes it too -- its sqrt blocks' upper halves are no
 # longer streamed (before: 512, below which the per-range launches cost more than the saved traffic).  Small toy
-# shapes keep the dense update, which also moves upper-triangle entries a synthetic gradient may carry;
-# NMGP_ADAM_LOWER_MIN_M overrides (A/B)
-ADAM_LOWER_MIN_M = int(os.environ.get("NMGP_ADAM_LOWER_MIN_M", "256"))
+# shapes keep the dense update, which also moves upper-triangle entries a synthetic gradient may carry
+ADAM_LOWER_MIN_M = 256
+
+# The engine's equivalence switches: NMGP_<name>=0 in the environment when an engine is built selects the reference
+# path that the fused / streamed path of that name is compared with bit for bit by the tests (DESIGN.md lists the
+# test of each).  Unset, or any other value: the default path.
+_SWITCHES = ("FUSE_TP", "FUSE_VG", "FUSE_HEAD", "KL_SOLVE", "BIG_SIDE", "PAIR_STREAM")
+
+
+def _switch(name):
+    assert name in _SWITCHES
+    return os.environ.get("NMGP_" + name, "1") != "0"
 
 
 def use_adam_lower(M, dtype, offs):
@@ -169,34 +178,31 @@ class DsviEngine:
         # padding.  NMGP_PAIR_STREAM=0 keeps them on the grouped kernels (tests' equivalence switch).
         n_out = (self.pair_range[1] - self.pair_range[0]) if self.pair_range is not None else D
         self.pair_stream = (self.Q > 0 and B <= 32 * max(1, n_out) and M % 4 == 0 and M <= 1024
-                            and os.environ.get("NMGP_PAIR_STREAM", "1") != "0")
-        self.big_side = self.dt == torch.float32 and M >= 512 and os.environ.get("NMGP_BIG_SIDE", "1") != "0"
-        # round 6: with big_side the row-segmented B x M x M products (W = P L, P-bar = W-hat L^T) run on the 128x128
-        # kernel too; NMGP_BIG_ROWS=0 keeps them on the grouped kernel (A/B and equivalence switch)
-        self.big_rows = self.big_side and os.environ.get("NMGP_BIG_ROWS", "1") != "0"
+                            and _switch("PAIR_STREAM"))
+        # HCP / ECoG shapes (fp32, M >= 512): the D+Q factor products run on the 128x128 f32 MFMA kernel at
+        # per-factor offsets (BigBatch) instead of the grouped 64x64 tiles, and since round 6 the row-segmented
+        # B x M x M products (W = P L, P-bar = W-hat L^T) too.  NMGP_BIG_SIDE=0 keeps them all on the grouped kernel,
+        # for tests/test_gpu_engine.py's equivalence check
+        self.big_side = self.dt == torch.float32 and M >= 512 and _switch("BIG_SIDE")
         # round 6: the KL L-bar of the variational factors in the solve form, Sigma^-1 L = C^-T (C^-1 L) applied
         # blockwise from the factor and the inverses of its two diagonal blocks (the recursion's top-level
         # off-diagonal inverse block, two products, is not formed: nmgp_chol_blockinv_batched_f32).  NMGP_KL_SOLVE=0
         # keeps the explicit-inverse form (A/B and equivalence switch)
-        self.kl_solve = (self.big_side and M > 256 and M % 128 == 0 and os.environ.get("NMGP_KL_SOLVE", "1") != "0")
+        self.kl_solve = (self.big_side and M > 256 and M % 128 == 0 and _switch("KL_SOLVE"))
         self._ones = torch.ones(M, dtype=self.dt, device=self.dev) if self.kl_solve else None
         # per-pair P-bar products W-hat_ij L_ij^T, slot j (pair kernels, or the 128x128 kernel at M >= 512)
-        self.Zp = e(D, B, M) if (self.pair_stream or (self.big_rows and self.Q > 0)) else None
-        # HCP / ECoG shapes (fp32, M >= 512): the D+Q factor products run on the 128x128 f32 MFMA kernel at
-        # per-factor offsets (BigBatch) instead of the grouped 64x64 tiles.  NMGP_BIG_SIDE=0 keeps them on the
-        # grouped kernel: the only schedule switch left, for tests/test_gpu_engine.py's equivalence check (set above,
-        # where the per-pair Z buffer is sized)
+        self.Zp = e(D, B, M) if (self.pair_stream or (self.big_side and self.Q > 0)) else None
         # round 6: fp64 engines of 128 <= M <= 256 run the GP priors as two fused launches (nmgp_chol_tp_f64): the
         # RBF priors' K22 built, factored and inverted with K12 / T / P of their rows formed by the same launch, and
         # likewise the Gibbs prior with its t-row sample -- no builder, invG / projG or t-row launches on the chain.
         # NMGP_FUSE_TP=0 keeps the separate launches (the tests' equivalence switch)
         self.fuse_tp = (self.dt == torch.float64 and 128 <= M <= 256 and B <= 4096
-                        and os.environ.get("NMGP_FUSE_TP", "1") != "0")
+                        and _switch("FUSE_TP"))
         # and the Gibbs prior's K22 from the first of them (NMGP_FUSE_VG=0: its own launch, dsvi_vg22)
-        self.fuse_vg = self.fuse_tp and os.environ.get("NMGP_FUSE_VG", "1") != "0"
+        self.fuse_vg = self.fuse_tp and _switch("FUSE_VG")
         # and a bound dataset's step starts with ONE launch, nmgp_step_head_*: step_begin, the RBF K22 builders and
         # Sigma_v as workgroups of one grid (NMGP_FUSE_HEAD=0: the three launches; the tests' equivalence switch)
-        self.fuse_head = self.fuse_tp and os.environ.get("NMGP_FUSE_HEAD", "1") != "0"
+        self.fuse_head = self.fuse_tp and _switch("FUSE_HEAD")
         # per-(output, factor) L-bar products of the grouped backward (bwd_lbar), summed by nmgp_lbar_reduce: D(D+1)/2
         # slots of M x M + M.  Only where the slots stay small (PM2.5: 15 slots, 7.9 MB); many outputs with few
         # rows each (HCP-like D = 50) keep one product per factor, whose k loop is then short anyway
@@ -274,6 +280,14 @@ class DsviEngine:
         self._theta = None
         self._plans = {}
         self._elbo_kl = None      # (f0, f1, with_v): compute_ELBO KL share (None: the whole model's)
+        self._row_order = None    # load_batch: the permutation that grouped the rows by output (None: identity)
+        self._dataset = None      # bind_dataset: (Xb, Yb, Ib, Sb, counter)
+        self._begin_done = None   # the first launch's completion counter (made on first use)
+        self._side = None         # the three side streams (made by the first run on streams)
+        # the installed training schedule: the launch list, the argument struct its closures pass (set_adam_step
+        # writes the counter pointer there) and the bindings it was built for (None: none installed)
+        self._sched, self._sched_args, self._sched_key = None, None, None
+        self._elbo_sched = {}     # compute_ELBO schedules by their key: (steps, args)
 
     def pidx(self, i, j):
         """Block index of coefficient pair (i, j) in mu_U / sqrt_U (dense i*D + j, or packed)."""
@@ -476,7 +490,7 @@ class DsviEngine:
             vg = None
             if not elbo_mode and self.fuse_vg:
                 vg = dict(muv=th.data_ptr() + muv * th.element_size(), z=self.noise, v=self.v, ellZ=self.ellZ,
-                          K22=self.Afac[NF + 3], wgs=int(os.environ.get("NMGP_VG_WGS", "8")))
+                          K22=self.Afac[NF + 3], wgs=8)
             p["chol_tp_main"] = H.CholTp(self.Afac[FV], self.Cinv[FV], self.info[FV:], M, [dict()] + rbf,
                                          jitter=self.jitter, Z=self.Z, x=self.x, B=B, vg=vg)
             p["chol_tp_G"] = H.CholTp(self.Afac[NF + 3], self.Cinv[NF + 3], self.info[NF + 3:], M,
@@ -515,7 +529,7 @@ class DsviEngine:
             # later Monte-Carlo samples of compute_ELBO: the pair factors W_P = P_{0,1} L_ij do not depend
             # on the sample (the L priors and Sigma_U are fixed within a call) -- only the D latent ones
             p["quad_W"] = G(d14[:D])
-        if self.big_rows:
+        if self.big_side:
             # fp32 M >= 512 (HCP): the quadratic-form factors W = P L on the 128x128 f32 kernel at per-factor offsets,
             # each problem's rows from the segment table (round 6: the grouped 64x64 kernel ran them at 21-28 TFLOP/s,
             # profiles/r04h_hcp_gemm_groups.jsonl).  Same products as d14.
@@ -558,7 +572,7 @@ class DsviEngine:
         # profiles/r03za_kt_cap_ab.txt.)
         p["bwd_wG"] = G(d17G)
         p["bwd_wP"] = G(d17P) if d17P else None
-        if self.big_rows:
+        if self.big_side:
             # fp32 M >= 512: Z_d = W-hat_d L_d^T (rows of outputs >= d) on the 128x128 kernel; the pair P-bar in the
             # per-pair form Z_ij = W-hat_ij L_ij^T into slot j (rows of output i), summed onto P-bar_0 / P-bar_1 in
             # j order by nmgp_pair_pbar_reduce (the k-blocked d17P products sum the same terms in one k loop)
@@ -803,7 +817,7 @@ class DsviEngine:
         nz = torch.as_tensor(noise, dtype=F64).reshape(-1)
         if nz.numel() != M + B + Q * B:
             raise ValueError(f"noise has {nz.numel()} values, the step draws M + B + Q*B = {M + B + Q * B}")
-        o = getattr(self, "_row_order", None)
+        o = self._row_order
         if o is not None:
             nz = torch.cat([nz[:M], nz[M:M + B][o], nz[M + B:].reshape(Q, B)[:, o].reshape(-1)])
         self.noise.copy_(nz.to(self.dt))
@@ -836,16 +850,15 @@ class DsviEngine:
         """Round 6: the training schedule's finalize launch advances `step` (an int64 device counter) at its end
         (nmgp_dsvi_args.adam_step; None: off).  Set around a capture only (DsviTrainer.capture), after the warm-up
         built the schedule: launches copy the argument struct when they are issued."""
-        ptr = None if step is None else ctypes.c_void_p(step.data_ptr())
-        for (elbo_mode, _), a in getattr(self, "_keep_args", {}).items():
-            if not elbo_mode:
-                a.adam_step = ptr
+        if self._sched_key is None:
+            raise RuntimeError("set_adam_step: no training schedule is installed (run forward_backward first)")
+        self._sched_args.adam_step = None if step is None else ctypes.c_void_p(step.data_ptr())
 
     def begin_step(self, seed, counter, stream=None):
         """Gather + device noise + noise-counter advance + gradient zeroing in one launch
         (nmgp_step_begin_*); the forward_backward that follows must not zero the gradient again."""
         Xb, Yb, Ib, Sb, ctr = self._dataset
-        if getattr(self, "_begin_done", None) is None:
+        if self._begin_done is None:
             self._begin_done = torch.zeros(1, dtype=torch.int32, device=self.dev)
         s = L.stream_handle() if stream is None else stream
         vp = ctypes.c_void_p
@@ -873,7 +886,7 @@ class DsviEngine:
         """begin_step + p["build_k22"] + p["syrk"] in one launch (nmgp_step_head_*; same values bit for bit)."""
         k22, sy = self.head_groups()
         Xb, Yb, Ib, Sb, ctr = self._dataset
-        if getattr(self, "_begin_done", None) is None:
+        if self._begin_done is None:
             self._begin_done = torch.zeros(1, dtype=torch.int32, device=self.dev)
         s = L.stream_handle() if stream is None else stream
         vp = ctypes.c_void_p
@@ -908,7 +921,9 @@ class DsviEngine:
         """The ordered launch list of one step.  Items are (name, kind, callable(stream), where) with where
         one of the four streams, plus ("sig", stream, tag) / ("wait", stream, tag) event edges: the D+Q
         variational factors that only the KL terms need are factored on a side stream, overlapping the
-        forward chain; the backward's independent chains run on three side streams."""
+        forward chain; the backward's independent chains run on three side streams.
+        Returns (steps, args): args is the one argument struct every row-kernel closure of `steps` passes, read when
+        a launch is issued and kept alive by those closures.  Nothing is stored on the engine."""
         lib = L.lib()
         D, M, NF = self.D, self.M, self.NF
         MM = M * M
@@ -916,8 +931,6 @@ class DsviEngine:
         fuse = self.fuse_tp
         p = self._plan(elbo_mode)
         a = self._args(elbo_mode)
-        self._keep_args = getattr(self, "_keep_args", {})
-        self._keep_args[(elbo_mode, with_kl)] = a
         Af, Ci, info = self.Afac.data_ptr(), self.Cinv.data_ptr(), self.info.data_ptr()
         vp = ctypes.c_void_p
 
@@ -1163,7 +1176,7 @@ class DsviEngine:
                 steps = [it for it in steps if not (len(it) == 4 and it[0] in skip)]
                 steps = [("quad_W",) + it[1:] if len(it) == 4 and it[0] == "quad" else it for it in steps]
                 steps = [(it[0], it[1], gemm("quad_W"), it[3]) if it[0] == "quad_W" else it for it in steps]
-            return steps
+            return steps, a
         # KL branch on the side stream once all prior factors and Y = A^-1 mu exist (after projG):
         # KL terms, prior-diagonal adjoints, the variational factors' KL L-bar (first writer of those
         # gradient rows -- bwd_lbar follows it on the same stream, so the accumulation order is fixed) and the
@@ -1287,7 +1300,7 @@ class DsviEngine:
         if D * M + M + self.NPC * M > MUGRAD_IN_FINALIZE_MAX:
             steps.append(("mugrad", "row", row(getattr(lib, "nmgp_dsvi_mugrad_" + self.sfx)), "main"))
         steps.append(("finalize", "row", row(getattr(lib, "nmgp_dsvi_finalize_" + self.sfx)), "main"))
-        return steps
+        return steps, a
 
     def _run(self, steps, stream, timer):
         """Enqueue `steps`.  timer=None: on the four streams.  A timer with concurrent=False: serially on
@@ -1298,7 +1311,7 @@ class DsviEngine:
         s_main = ctypes.c_void_p(main.cuda_stream)
         conc = timer is not None and getattr(timer, "concurrent", False)
         if timer is None or conc:
-            if getattr(self, "_side", None) is None:
+            if self._side is None:
                 self._side = torch.cuda.Stream(device=self.dev)
                 self._side2 = torch.cuda.Stream(device=self.dev)
                 self._side3 = torch.cuda.Stream(device=self.dev)
@@ -1347,8 +1360,8 @@ class DsviEngine:
         """Enqueue -SELBO (self.out[0]) and all gradients (into the bound grad vector); head: the step was begun by
         head_step, which formed K22 + lam I and Sigma_v + lam I already."""
         key = ("fb", self._theta.data_ptr(), self._grad.data_ptr(), self.frozen_mask, self.N)
-        if getattr(self, "_sched_key", None) != key:
-            self._sched = self._schedule(0)
+        if self._sched_key != key:
+            self._sched, self._sched_args = self._schedule(0)
             self._sched_head = self._head_schedule(self._sched)
             self._sched_key = key
         if zero_grad:
@@ -1366,11 +1379,9 @@ class DsviEngine:
         K_G22: only the owner of the last sample may include them)."""
         self._elbo_kl = None if kl_part is None else (int(kl_part[0]), int(kl_part[1]), bool(kl_part[2]))
         key = ("elbo", with_kl, cached, self._theta.data_ptr(), self.frozen_mask, self.N, self._elbo_kl)
-        cache = getattr(self, "_elbo_sched", {})
-        if key not in cache:
-            cache[key] = self._schedule(1, with_kl, cached)
-            self._elbo_sched = cache
-        self._run(cache[key], stream, None)
+        if key not in self._elbo_sched:
+            self._elbo_sched[key] = self._schedule(1, with_kl, cached)
+        self._run(self._elbo_sched[key][0], stream, None)
         return self.out
 
     def _kl_solve_xs(self, th, slots, offs_f):
@@ -1445,9 +1456,10 @@ class DsviEngine:
                           flags=flags, rseg=(self.seg, [r for r, _ in rows], [s_ for _, s_ in rows]))
 
     def gemm_groups(self):
-        """(name, GemmGroup) of the training step, for FLOP accounting."""
+        """(name, GemmGroup) of the training step, for FLOP accounting.  (The launch list built here to name them is
+        dropped: the installed schedule and its argument struct are not touched.)"""
         p = self._plan(0)
-        return [(it[0], p[it[0]]) for it in self._schedule(0) if len(it) > 1 and it[1] == "gemm"]
+        return [(it[0], p[it[0]]) for it in self._schedule(0)[0] if len(it) > 1 and it[1] == "gemm"]
 
     def check_info(self):
         info = self.info.cpu()

@@ -3,7 +3,6 @@
 Everything here enqueues HIP kernels on torch's current stream; nothing falls back to CPU math.
 """
 import ctypes
-import os
 import math
 
 import torch
@@ -107,8 +106,9 @@ _LAT_MAX_ROUNDS = 2
 # round of workgroups (two 8-wave workgroups per CU): "auto", "0" (never), "force" (every latency-kernel group).
 # Off by default: measured on the PM2.5 step (round 6, gpurun_out r06l) it LOST -- one workgroup per CU (the second
 # operand buffer needs ~210 VGPRs) leaves 8 waves per CU where the one-tile kernel keeps 16, and the reduction /
-# epilogue phases then idle the matrix cores: bwd_wG 72 -> 135 us, bwd_lbar 100 -> 174 us, step 0.68 -> 0.83 ms
-_LAT_PIPE = os.environ.get("NMGP_LAT_PIPE", "0")
+# epilogue phases then idle the matrix cores: bwd_wG 72 -> 135 us, bwd_lbar 100 -> 174 us, step 0.68 -> 0.83 ms.
+# No environment switch selects it: only the tests set this, to compare the two launch forms bit for bit.
+_LAT_PIPE = "0"
 LAT_ROUND_WGS = 512
 
 

@@ -1271,7 +1271,7 @@ def test_training_step_graph_is_captured_through_hip(ops):
         if graph:
             g = tr.capture(eng, include_update=False)
             assert isinstance(g, ops.HipGraph)
-            sched = eng._schedule(0)
+            sched, _ = eng._schedule(0)
             sig = {it[2]: it[1] for it in sched if it[0] == "sig"}
             waits = [(it[1], sig[it[2]]) for it in sched if it[0] == "wait"]
             assert ("side", "side2") in waits and ("side2", "side") not in waits
@@ -1289,35 +1289,78 @@ def test_captured_step_folded_counter_matches_counter_launch(ops, monkeypatch, d
     (nmgp_dsvi_args.adam_step) and the update reading it (nmgp_adam_lower_advanced_*) equals the step with the
     counter's own launch (DsviTrainer.FOLD_STEP = False) bit for bit after three replays: theta, m, v, and the
     counter = 3 (M = 256 fp64: the fused prior schedule; fp32 M = 512).  Eager steps afterwards are unaffected
-    (the counter is advanced once per update, by update())."""
-    from collaborative_nonstationary_multivariate_gaussian_process_amd.nmgp_dsvi import NMGP, DsviTrainer
-    rng = np.random.default_rng(21)
-    D, B, nb = 3, 240, 2
+    (the counter is advanced once per update, by update()): the pointer is cleared after the capture.  Inside the
+    capture the struct that received the pointer is the one the installed schedule's closures pass."""
+    from collaborative_nonstationary_multivariate_gaussian_process_amd.nmgp_dsvi import DsviTrainer
+    from collaborative_nonstationary_multivariate_gaussian_process_amd import _lib as L
     res = []
     for fold in (True, False):
         monkeypatch.setattr(DsviTrainer, "FOLD_STEP", fold)
-        model = NMGP(number_observations=D * 400, dim_outputs=D, Z=np.linspace(0, 1, M), minibatch_size=B, seed=9,
-                     device=DEV, noise="device", dtype=dt)
-        tr = DsviTrainer(model, 0.01)
-        eng = model.engine(B)
-        g = np.random.default_rng(4)
-        Xb = torch.tensor(g.uniform(0, 1, (nb, B)), dtype=dt, device=DEV)
-        Yb = torch.tensor(g.standard_normal((nb, B)), dtype=dt, device=DEV)
-        ids = np.sort(g.integers(0, D, (nb, B)), axis=1)
-        Ib = torch.tensor(ids, dtype=torch.int32, device=DEV)
-        Sb = torch.tensor(np.stack([np.concatenate([[0], np.cumsum(np.bincount(r, minlength=D))]) for r in ids]),
-                          dtype=torch.int32, device=DEV)
-        eng.bind_dataset(Xb, Yb, Ib, Sb)
+        model, tr, eng = _folded_step_setup(dt, M)
+        seen = []
+        set_adam_step = eng.set_adam_step
+
+        def spy(step):
+            set_adam_step(step)
+            if step is not None:
+                fin = [it[2] for it in eng._sched if it[0] == "finalize"][-1]
+                used = [c.cell_contents for c in fin.__closure__ if isinstance(c.cell_contents, L.DsviArgs)]
+                seen.append((used, eng._sched_args.adam_step, step.data_ptr()))
+        monkeypatch.setattr(eng, "set_adam_step", spy)
         graph = tr.capture(eng, include_update=True)
         for _ in range(3):
             graph.replay()
         torch.cuda.synchronize()
-        assert all(getattr(a, "adam_step", None) in (None, 0) for a in eng._keep_args.values())
+        assert len(seen) == (1 if fold else 0)
+        for used, got, ptr in seen:
+            assert len(used) == 1 and used[0] is eng._sched_args and got == ptr != 0
+        assert eng._sched_args.adam_step in (None, 0)
         res.append((model._theta.detach().cpu().clone(), tr.m.cpu().clone(), tr.v.cpu().clone(),
                     int(tr.step_count.item())))
     for a, b in zip(res[0][:3], res[1][:3]):
         assert torch.equal(a, b)
     assert res[0][3] == res[1][3] == 3
+
+
+def _folded_step_setup(dt, M):
+    """A model, its trainer and an engine with a two-minibatch dataset bound (D = 3, B = 240)."""
+    from collaborative_nonstationary_multivariate_gaussian_process_amd.nmgp_dsvi import NMGP, DsviTrainer
+    D, B, nb = 3, 240, 2
+    model = NMGP(number_observations=D * 400, dim_outputs=D, Z=np.linspace(0, 1, M), minibatch_size=B, seed=9,
+                 device=DEV, noise="device", dtype=dt)
+    tr = DsviTrainer(model, 0.01)
+    eng = model.engine(B)
+    g = np.random.default_rng(4)
+    Xb = torch.tensor(g.uniform(0, 1, (nb, B)), dtype=dt, device=DEV)
+    Yb = torch.tensor(g.standard_normal((nb, B)), dtype=dt, device=DEV)
+    ids = np.sort(g.integers(0, D, (nb, B)), axis=1)
+    Ib = torch.tensor(ids, dtype=torch.int32, device=DEV)
+    Sb = torch.tensor(np.stack([np.concatenate([[0], np.cumsum(np.bincount(r, minlength=D))]) for r in ids]),
+                      dtype=torch.int32, device=DEV)
+    eng.bind_dataset(Xb, Yb, Ib, Sb)
+    return model, tr, eng
+
+
+def test_captured_folded_step_survives_gemm_groups_before_capture(ops):
+    """An eager step, then DsviEngine.gemm_groups(), then the capture: listing the groups builds a launch list of its
+    own and must leave the installed schedule's argument struct the one set_adam_step writes -- else the captured
+    finalize launch gets no counter, the folded update runs with t = 0 (1 - beta^0 = 0) and theta becomes non-finite.
+    fp64, M = 256 (the smallest M with the folded update), D = 3, B = 240, two minibatches; three replays: the counter
+    is 3 and theta, m, v are finite and equal, bit for bit, the same sequence without the gemm_groups() call."""
+    res = []
+    for listed in (True, False):
+        model, tr, eng = _folded_step_setup(F64, 256)
+        tr.grad_step(eng)
+        if listed:
+            assert len(eng.gemm_groups()) > 0
+        graph = tr.capture(eng, include_update=True)
+        for _ in range(3):
+            graph.replay()
+        torch.cuda.synchronize()
+        assert int(tr.step_count.item()) == 3
+        res.append((model._theta.detach().cpu().clone(), tr.m.cpu().clone(), tr.v.cpu().clone()))
+    for a, b in zip(*res):
+        assert torch.isfinite(a).all() and torch.equal(a, b)
 
 
 def test_hip_graph_external_event_node_fires_mid_replay(ops):

@@ -4,7 +4,7 @@
 LEG=${LEG:-hcp}
 if [ "$LEG" = ecog ]; then SKIP=--no-hcp; KEY="d['ecog_train']['s_per_step']"; else SKIP=--no-ecog; KEY="d['hcp_train']['it_per_s']"; fi
 A="--full --steps 20 --warmup 5 --no-cpu-baseline --no-stress --no-elbo --no-api --no-kron --no-breakdown $SKIP"
-VARIANTS=${VARIANTS:-"NMGP_BIG_ROWS=0|NMGP_BIG_ROWS=1"}
+VARIANTS=${VARIANTS:-"NMGP_BIG_SIDE=0|NMGP_BIG_SIDE=1"}
 for rep in 1 2; do
 IFS='|'; for v in $VARIANTS; do
   unset IFS

@@ -1,5 +1,5 @@
 // Phase-level timing of the batched potrf/trtri kernels (standalone; not part of the library).
-//   hipcc -O3 --offload-arch=gfx950 -DNMGP_CHOL_TRACE -I<pkg>/csrc -Iinclude tools/chol_probe.hip <pkg>/csrc/gemm.hip -o /tmp/chol_probe
+//   hipcc -O3 --offload-arch=gfx950 -DNMGP_CHOL_TRACE -I<pkg>/csrc -Iinclude tools/chol_probe.hip <pkg>/csrc/gemm.hip <pkg>/csrc/gemm_big.hip -o /tmp/chol_probe
 //   ./chol_probe [n] [batch]
 // Prints kernel times (hipEvents, averaged) and, for potrf, the per-block-step split of wall-clock
 // time between phase 1 (diagonal factor), phase 2 (panel) and phase 3 (trailing update).

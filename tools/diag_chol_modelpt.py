@@ -9,7 +9,7 @@ from collaborative_nonstationary_multivariate_gaussian_process_amd import hip_op
 case = sys.argv[1] if len(sys.argv) > 1 else "modelpt_forward"
 g, xs, ys, p, eng, theta, grad = _setup(case)
 saved = {}
-sched = eng._schedule(0)
+sched, _ = eng._schedule(0)
 new = []
 for it in sched:
     if len(it) > 1 and it[1] == "chol":
