@@ -247,6 +247,9 @@ _SIGS = {
     "nmgp_corr_spectrum_workspace_bytes": (c_i64, [c_int, c_int, c_int, c_int]),
     "nmgp_corr_spectrum_f64": (c_int, [c_vp, c_vp, c_i64, c_vp, c_i64, c_int, c_int, c_int, c_int, c_vp, c_i64, c_i64,
                                        c_vp, c_vp, c_i64, c_vp, c_vp]),
+    "nmgp_mix_score_workspace_size": (c_i64, [c_int, c_i64]),
+    "nmgp_mix_score_f64": (c_int, [c_vp, c_i64, c_vp, c_i64, c_dbl, c_int, c_i64, c_vp, c_vp, c_vp, c_int, c_vp, c_vp,
+                                   c_vp, c_vp, c_i64, c_vp, c_vp, c_i64, c_vp]),
     "nmgp_counter_add": (c_int, [c_vp, c_i64, c_vp]),
     "nmgp_pbar_reduce_f64": (c_int, [c_vp, c_i64, c_vp, c_i64, c_vp, c_int, c_int, c_int, c_vp]),
     "nmgp_pbar_reduce_f32": (c_int, [c_vp, c_i64, c_vp, c_i64, c_vp, c_int, c_int, c_int, c_vp]),

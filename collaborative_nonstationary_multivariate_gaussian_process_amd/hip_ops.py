@@ -1479,5 +1479,112 @@ def y_accum_(pair_mu, pair_sd, G, z_p, z_f, I, sd_err, Y, F, F_sum, F_sq, L_sum,
                                  L.stream_handle()), "y_accum")
 
 
+MIX_MAX_Q = 16            # quantiles per mix_score_ call (csrc/mixscore.hip kMsMaxQ)
+MIX_MAX_S = 1 << 20       # components per entry (kMsMaxS)
+
+
+def check_mix_args(Mu, Var, y=None, qs=()):
+    """The argument checks of mix_score_ that need no device -> (S, E, list of probabilities); ValueError otherwise.
+    Mu (S, E) float64 with unit column stride (a column range of a wider buffer is fine); Var the same shape, or one
+    positive finite number; y (E,); every probability strictly inside (0, 1), at most MIX_MAX_Q of them."""
+    if not torch.is_tensor(Mu) or Mu.dtype != torch.float64 or Mu.dim() != 2:
+        raise ValueError("Mu must be a float64 (S, E) tensor")
+    S, E = Mu.shape
+    if not 1 <= S <= MIX_MAX_S:
+        raise ValueError(f"Mu needs 1 <= S <= {MIX_MAX_S} components, got {S}")
+
+    def rows_ok(t):
+        return (t.stride(1) == 1 or E <= 1) and (S == 1 or t.stride(0) >= E)
+
+    if not rows_ok(Mu):
+        raise ValueError("Mu must have unit column stride and a row stride >= E")
+    if torch.is_tensor(Var) and Var.dim() > 0:
+        if Var.dtype != torch.float64 or Var.shape != Mu.shape or not rows_ok(Var) or Var.device != Mu.device:
+            raise ValueError("Var must be a float64 tensor of Mu's shape and device, unit column stride")
+    else:
+        v = float(Var)
+        if not (v > 0.0 and v != float("inf")):
+            raise ValueError(f"a scalar variance must be positive and finite, got {v}")
+    if y is not None:
+        if not torch.is_tensor(y) or y.dtype != torch.float64 or y.shape != (E,) or y.device != Mu.device:
+            raise ValueError(f"y must be a float64 ({E},) tensor on Mu's device")
+    try:
+        ps = [float(q) for q in qs]
+    except (TypeError, ValueError):
+        raise ValueError("quantiles must be a sequence of numbers") from None
+    if len(ps) > MIX_MAX_Q:
+        raise ValueError(f"at most {MIX_MAX_Q} quantiles per call, got {len(ps)}")
+    if any(not 0.0 < q < 1.0 for q in ps):
+        raise ValueError("every quantile must lie strictly inside (0, 1)")
+    return S, E, ps
+
+
+def mix_score_workspace(S, E, device):
+    """Workspace of mix_score_ with crps=True for (S, E) component buffers (the slices' pair sums), or None where
+    there is nothing to slice (S = 1 or E = 0)."""
+    need = L.lib().nmgp_mix_score_workspace_size(int(S), int(E))
+    return torch.empty(need, dtype=torch.uint8, device=device) if need > 0 else None
+
+
+def mix_score_(Mu, Var_or_float, y=None, qs=(), crps=True, ws=None, out=None):
+    """Exact scores of E equal-weight mixtures of S Gaussians (csrc/mixscore.hip).  Mu (S, E): component means,
+    the component axis the slow one; Var_or_float: their variances (S, E), or one variance for all.  Both may be
+    column ranges of wider buffers.  Returns a dict of device tensors: with crps "spread" (E,), the term
+    (1 / 2 S^2) sum_s sum_t A(mu_s - mu_t, v_s + v_t); with y (E,) "pit" (the mixture CDF at y) and, with crps,
+    "crps"; with probabilities qs "quantiles" (len(qs), E), the exact roots of the mixture CDF, and "unconverged"
+    (1,) int32, the quantiles that did not reach adjacent doubles (NaN there).  An entry with a non-finite mean or
+    a variance that is not finite and positive is NaN throughout; a non-finite y[e] makes pit[e] and crps[e] NaN.
+    out: tensors to write into instead of new ones, by the same keys ((E,) slices of wider vectors, "quantiles" with
+    a row stride; "unconverged" is added to).  ws: mix_score_workspace(S, E, device), else allocated here.
+    Argument errors raise ValueError before any device work."""
+    S, E, ps = check_mix_args(Mu, Var_or_float, y, qs)
+    L.require_device(Mu, "Mu")
+    het = torch.is_tensor(Var_or_float) and Var_or_float.dim() > 0
+    dev, out = Mu.device, dict(out or {})
+    want = (["spread"] if crps else []) + (["pit"] if y is not None else []) + \
+           (["crps"] if crps and y is not None else [])
+    res = {}
+    for k in want:
+        t = out.get(k)
+        if t is None:
+            t = torch.empty(E, dtype=torch.float64, device=dev)
+        elif t.dtype != torch.float64 or t.shape != (E,) or t.device != dev or not (E <= 1 or t.stride(0) == 1):
+            raise ValueError(f"out[{k!r}] must be a float64 ({E},) device tensor with unit stride")
+        res[k] = t
+    nq, ld_q = len(ps), E
+    if nq:
+        t = out.get("quantiles")
+        if t is None:
+            t = torch.empty(nq, E, dtype=torch.float64, device=dev)
+        elif t.dtype != torch.float64 or t.shape != (nq, E) or t.device != dev or not (E <= 1 or t.stride(1) == 1) \
+                or not (nq == 1 or t.stride(0) >= E):
+            raise ValueError(f"out['quantiles'] must be a float64 ({nq}, {E}) device tensor, unit column stride")
+        res["quantiles"] = t
+        ld_q = t.stride(0) if nq > 1 else max(E, 1)
+        u = out.get("unconverged")
+        if u is None:
+            u = torch.zeros(1, dtype=torch.int32, device=dev)
+        elif u.dtype != torch.int32 or u.numel() != 1 or u.device != dev:
+            raise ValueError("out['unconverged'] must be a 1-element int32 device tensor")
+        res["unconverged"] = u
+    if not res:
+        raise ValueError("nothing to do: neither crps nor y nor quantiles")
+    if y is not None and not (E <= 1 or y.stride(0) == 1):
+        y = y.contiguous()
+    lib = L.lib()
+    need = lib.nmgp_mix_score_workspace_size(S, E) if crps else 0
+    ws = _ws_or_alloc(ws, need, dev)
+    zp = torch.special.ndtri(torch.tensor(ps, dtype=torch.float64)).tolist() if nq else []
+    arr = lambda vals: ctypes.cast((ctypes.c_double * max(1, nq))(*vals), ctypes.c_void_p)
+    ld = lambda t: t.stride(0) if S > 1 else max(E, 1)
+    L.check(lib.nmgp_mix_score_f64(L.ptr(Mu), ld(Mu), L.ptr(Var_or_float) if het else None,
+                                   ld(Var_or_float) if het else 0, 0.0 if het else float(Var_or_float), S, E,
+                                   L.ptr(y) if y is not None else None, arr(zp), arr(ps), nq, L.ptr(res.get("pit")),
+                                   L.ptr(res.get("crps")), L.ptr(res.get("spread")), L.ptr(res.get("quantiles")),
+                                   ld_q, L.ptr(res.get("unconverged")), L.ptr(ws) if need > 0 else None, need,
+                                   L.stream_handle()), "mix_score")
+    return res
+
+
 def counter_add_(counter, inc):
     L.check(L.lib().nmgp_counter_add(ctypes.c_void_p(counter.data_ptr()), int(inc), L.stream_handle()), "counter")

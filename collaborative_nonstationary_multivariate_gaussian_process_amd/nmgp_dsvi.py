@@ -1066,26 +1066,28 @@ def summarize_FY(model, x, n_sample=1000, quantiles=(0.025, 0.975), corr_pairs=N
     return {k: v.cpu().numpy() for k, v in out.items()}
 
 
-def summarize_Y(model, X_list, Y_list=None, n_sample=1000, index=None, quantiles=(0.025, 0.975)):
+def summarize_Y(model, X_list, Y_list=None, n_sample=1000, index=None, quantiles=(0.025, 0.975), mixture=False):
     """What the reference's drivers make of sample_Y on held-out rows (NMGP_ECoG_pred.py:277-299): means, sds and
     quantile bands per row and, with the observations Y_list, log predictive density, RMSE and coverage -- a dict
-    of numpy arrays (predict.summarize_Y; the (S, D, D, N) pair tensor of sample_Y is never built)."""
+    of numpy arrays (predict.summarize_Y; the (S, D, D, N) pair tensor of sample_Y is never built).  mixture=True
+    adds the exact scores of the rows' Gaussian-mixture predictives: their own quantiles, CRPS, PIT and coverage."""
     from . import predict
     to = lambda lst: [torch.from_numpy(np.asarray(a)).to(F64) for a in lst]
     out = predict.summarize_Y(model, to(X_list), None if Y_list is None else to(Y_list), n_sample=n_sample,
-                              index=index, quantiles=quantiles)
+                              index=index, quantiles=quantiles, mixture=mixture)
     return {k: v.cpu().numpy() for k, v in out.items()}
 
 
-def impute_Y(model, x, Y_obs, Y_true=None, n_sample=1000, quantiles=(0.025, 0.975)):
+def impute_Y(model, x, Y_obs, Y_true=None, n_sample=1000, quantiles=(0.025, 0.975), mixture=False):
     """The missing outputs at the inputs x predicted from the outputs observed at the same inputs (Y_obs (N, D),
     NaN where missing; predict.observed_grid builds it from per-output lists): mixture mean, sd and quantile bands
     per missing entry and, with Y_true, log predictive density, RMSE and coverage -- a dict of numpy arrays
-    (predict.impute_Y; one fused launch per chunk, no (S, N, D, D) tensor)."""
+    (predict.impute_Y; one fused launch per chunk, no (S, N, D, D) tensor).  mixture=True adds the exact scores of
+    the entries' Gaussian-mixture predictives: their own quantiles, CRPS, PIT and coverage."""
     from . import predict
     out = predict.impute_Y(model, torch.from_numpy(np.asarray(x, np.float64)), np.asarray(Y_obs, np.float64),
                            None if Y_true is None else np.asarray(Y_true, np.float64), n_sample=n_sample,
-                           quantiles=quantiles)
+                           quantiles=quantiles, mixture=mixture)
     return {k: v.cpu().numpy() for k, v in out.items()}
 
 

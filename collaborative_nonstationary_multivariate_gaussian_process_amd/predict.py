@@ -740,8 +740,42 @@ def summarize_FY(model, x, n_sample=1000, quantiles=(0.025, 0.975), noise_tape=N
     return out
 
 
+def score_mixture(Mu, Var, y=None, quantiles=(), crps=True):
+    """Exact scores of E predictives that are equal-weight mixtures of S Gaussians -- what summarize_Y (components
+    N(F_sn, s2)) and impute_Y (components N(mu_se, v_se)) end in -- from the component buffers, e.g. the
+    keep_samples outputs: Mu (S, E) float64 device tensor, Var the same shape or one positive number.  One fused
+    pass (csrc/mixscore.hip), closed forms throughout, no Monte-Carlo noise.  A dict of device tensors:
+    with crps=True "crps_spread" (E,), the term (1 / 2 S^2) sum_s sum_t A(mu_s - mu_t, v_s + v_t) of the CRPS that
+    needs no truth; with y (E,) "pit" (E,), the mixture CDF at the truth, and with crps=True also "crps" (E,) and
+    "mean_crps" over the entries with a finite y (0 / 0 = NaN, like mean_lpd); with quantiles (probabilities
+    strictly inside (0, 1)) "quantiles" (len(quantiles), E), the exact roots of the mixture CDF, bisected down to
+    adjacent doubles, and "unconverged" (1,) int32, the number of quantiles that did not get there (NaN; 0 in every
+    case tried).  An entry with a non-finite mean or a variance that is not finite and positive is NaN throughout;
+    a non-finite y[e] makes pit[e] and crps[e] NaN only.  Argument errors raise ValueError before any device
+    work."""
+    got = H.mix_score_(Mu, Var, y=y, qs=quantiles, crps=crps)
+    out = {}
+    if "pit" in got:
+        out["pit"] = got["pit"]
+    if "crps" in got:
+        c, ok = got["crps"], torch.isfinite(y)
+        out["crps"] = c
+        out["mean_crps"] = torch.where(ok, c, torch.zeros_like(c)).sum() / ok.sum()
+    if "spread" in got:
+        out["crps_spread"] = got["spread"]
+    if "quantiles" in got:
+        out["quantiles"], out["unconverged"] = got["quantiles"], got["unconverged"]
+    return out
+
+
+def _mixture_coverage(Mq, qs, y):
+    """1 where y lies inside the outermost pair of the exact quantiles Mq (len(qs), E), else 0, as float64."""
+    lo, hi = Mq[int(np.argmin(qs))], Mq[int(np.argmax(qs))]
+    return ((y >= lo) & (y <= hi)).to(F64)
+
+
 def summarize_Y(model, X_list, Y_list=None, n_sample=1000, index=None, quantiles=(0.025, 0.975), noise_tape=None,
-                keep_samples=False):
+                keep_samples=False, mixture=False):
     """What the reference's drivers keep of NMGP.sample_Y on held-out rows (code/nmgp_dsvi.py:406-490;
     NMGP_ECoG_pred.py:277-299): mean, population sd and quantile bands of Y, mean and sd of the noise-free F, of
     row I_n of L and of G, mean and bands of tilde_ell -- and, when the observations Y_list are given, the scores:
@@ -750,7 +784,14 @@ def summarize_Y(model, X_list, Y_list=None, n_sample=1000, index=None, quantiles
     not finite are left out of every score and keep a NaN lpd).  A dict of device tensors.  Same setup, chunking,
     noise layout and stream as sample_Y; each chunk's tail is one fused call (csrc/ysum.hip) that reads only the
     I_n + 1 pairs of row n, so O(S N + N D) is stored and the (S, D, D, N) tensor of sample_Y is not.
-    keep_samples=True adds Ys, Fs and tilde_ells, each (S, N)."""
+    keep_samples=True adds Ys, Fs and tilde_ells, each (S, N).
+
+    mixture=True adds the exact scores of the rows' predictives, the equal-weight mixtures of N(F_sn, s2) with
+    s2 = sigma2_err + 1e-4 (score_mixture on Fs, one launch after the last chunk; the Y bands above are order
+    statistics of one noisy draw per sample, these are the mixture's own): "mixture_quantiles" (len(quantiles), N),
+    "crps_spread" (N,), "mixture_unconverged" (1,), and with Y_list "pit" and "crps" (N,), "mean_crps",
+    "crps_per_entry" and "mixture_coverage" per list entry (the outermost pair of exact quantiles; NaN with fewer
+    than two).  Every other key has the bits of the mixture=False run."""
     qs, n_sample = _check_sampling_args(quantiles, n_sample)
     D = model.D
     ids = list(range(len(X_list))) if index is None else [int(j) for j in index]
@@ -811,6 +852,16 @@ def summarize_Y(model, X_list, Y_list=None, n_sample=1000, index=None, quantiles
             lo, hi = Yq[int(np.argmin(qs))], Yq[int(np.argmax(qs))]
             inside = ((y >= lo) & (y <= hi)).to(F64)
             out["coverage"] = torch.stack([mean_of(inside[p], ok[p]) for p in parts])
+    if mixture:
+        mx = score_mixture(Fs, float(st["s2_err"] + JIT), y=y, quantiles=qs, crps=True)
+        Mq = mx.get("quantiles", torch.empty(0, N, dtype=F64, device=dev))
+        out["mixture_quantiles"], out["crps_spread"] = Mq, mx["crps_spread"]
+        out["mixture_unconverged"] = mx.get("unconverged", torch.zeros(1, dtype=torch.int32, device=dev))
+        if y is not None:
+            out["pit"], out["crps"], out["mean_crps"] = mx["pit"], mx["crps"], mx["mean_crps"]
+            out["crps_per_entry"] = torch.stack([mean_of(mx["crps"][p], ok[p]) for p in parts])
+            inside = _mixture_coverage(Mq, qs, y) if len(qs) >= 2 else torch.full_like(y, float("nan"))
+            out["mixture_coverage"] = torch.stack([mean_of(inside[p], ok[p]) for p in parts])
     if keep_samples:
         out["Ys"], out["Fs"], out["tilde_ells"] = Ys, Fs, Ts
     return out
@@ -852,7 +903,7 @@ def _impute_args(D, Y_obs, Y_true, n_sample, quantiles, N=None):
 
 
 def impute_Y(model, x, Y_obs, Y_true=None, n_sample=1000, quantiles=(0.025, 0.975), noise_tape=None,
-             keep_samples=False):
+             keep_samples=False, mixture=False):
     """Predict the missing outputs at the inputs x (N,) from the outputs observed at the SAME inputs: Y_obs (N, D)
     holds the observations, NaN where an output is missing (observed_grid builds it from per-output lists).  This
     is what makes the model collaborative at prediction time: the outputs share the latent g through L(x), so an
@@ -869,13 +920,19 @@ def impute_Y(model, x, Y_obs, Y_true=None, n_sample=1000, quantiles=(0.025, 0.97
     (n, d); "mean" and "sd" (mixture mean and population sd of y); "F_mean" and "F_sd" (noise-free: v_s - s2);
     "Y_filled" (N, D), Y_obs with the means written into the gaps; "tilde_ell_mean" (N,); with non-empty quantiles
     "quantiles" (len(quantiles), E), the sample quantiles of the draws mu_s + sqrt(v_s) z_f with z_f the entry's
-    noise of the sample_FY slot (one draw per sample, not the exact mixture quantile).  mu_s and v_s are collected
-    as (S, E) only when quantiles or keep_samples ask for them: 16 S E bytes, not batched.  keep_samples=True
-    adds "Mu", "Var" (S, E) and "tilde_ells" (S, N).
+    noise of the sample_FY slot (one draw per sample, not the exact mixture quantile: mixture=True gives that).
+    mu_s and v_s are collected as (S, E) only when quantiles, keep_samples or mixture ask for them: 16 S E bytes,
+    not batched.  keep_samples=True adds "Mu", "Var" (S, E) and "tilde_ells" (S, N).
+
+    mixture=True scores the collected mixtures exactly, once after the last chunk (score_mixture, csrc/mixscore.hip):
+    "mixture_quantiles" (len(quantiles), E), the roots of the mixture CDF, "crps_spread" (E,), the CRPS term that
+    needs no truth, and "mixture_unconverged" (1,); every other key keeps the bits of the mixture=False run.
 
     With Y_true (N, D) the missing entries whose truth is finite are scored: "lpd" (E,) the log of the mixture
     density at the truth (NaN where not scored) and "mean_lpd"; "rmse" (D,) per output and "rmse_all", of "mean";
-    "coverage" (D,) of the outermost quantile band (needs two quantiles); "n_scored" (D,).
+    "coverage" (D,) of the outermost quantile band (needs two quantiles); "n_scored" (D,).  With mixture=True also
+    "pit" (E,), the mixture CDF at the truth, "crps" (E,) and "mean_crps", "crps_per_output" (D,) and
+    "mixture_coverage" (D,) of the outermost pair of exact quantiles (NaN with fewer than two).
 
     A row with no missing entry costs nothing; with no missing entry at all every result has E = 0.  An all-NaN
     Y_obs conditions on nothing: the result is the unconditional predictive of sample_FY's Y, Rao-Blackwellised
@@ -900,7 +957,7 @@ def impute_Y(model, x, Y_obs, Y_true=None, n_sample=1000, quantiles=(0.025, 0.97
     flat = missing[:, 0] * D + missing[:, 1]
     z = lambda *shape: torch.zeros(*shape, dtype=F64, device=dev)
     mu_sum, y2_sum, f2_sum, T_sum = z(E), z(E), z(E), z(N)
-    collect = bool(qs) or keep_samples
+    collect = bool(qs) or keep_samples or mixture
     Mu = Var = Yd = None
     if collect:
         Mu, Var = torch.empty(n_sample, E, dtype=F64, device=dev), torch.empty(n_sample, E, dtype=F64, device=dev)
@@ -954,6 +1011,16 @@ def impute_Y(model, x, Y_obs, Y_true=None, n_sample=1000, quantiles=(0.025, 0.97
         if len(qs) >= 2:
             lo, hi = Yq[int(np.argmin(qs))], Yq[int(np.argmax(qs))]
             out["coverage"] = per_output(((y >= lo) & (y <= hi)).to(F64)) / n_sc
+    if mixture:
+        mx = score_mixture(Mu, Var, y=y, quantiles=qs, crps=True)
+        Mq = mx.get("quantiles", torch.empty(0, E, dtype=F64, device=dev))
+        out["mixture_quantiles"], out["crps_spread"] = Mq, mx["crps_spread"]
+        out["mixture_unconverged"] = mx.get("unconverged", torch.zeros(1, dtype=torch.int32, device=dev))
+        if y is not None:
+            out["pit"], out["crps"], out["mean_crps"] = mx["pit"], mx["crps"], mx["mean_crps"]
+            out["crps_per_output"] = per_output(mx["crps"]) / n_sc
+            inside = _mixture_coverage(Mq, qs, y) if len(qs) >= 2 else torch.full_like(y, float("nan"))
+            out["mixture_coverage"] = per_output(inside) / n_sc
     if keep_samples:
         out["Mu"], out["Var"], out["tilde_ells"] = Mu, Var, Ts
     return out

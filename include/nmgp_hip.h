@@ -882,6 +882,44 @@ int nmgp_corr_spectrum_f64(const double* pair_mu, const double* pair_sd, int64_t
                            int64_t z_stride, int D, int N, int S, int k, double* E, int64_t ld_e, int64_t s_off,
                            double* load2_sum, void* ws, int64_t ws_bytes, int32_t* unconverged, hipStream_t stream);
 
+/* Exact scores of equal-weight Gaussian mixtures (csrc/mixscore.hip): CRPS, PIT and quantiles of the predictives of
+ * nmgp_y_accum_f64 (components N(F_sn, s2)) and nmgp_ycond_accum_f64 (components N(mu_se, v_se)).  The reference has
+ * no such code.  fp64, no matrix cores.  Entry e < E has the S components mu_s = Mu[s * ld_mu + e] and
+ * v_s = Var[s * ld_var + e] (the component axis is the slow one, as the collected buffers lie; ld >= E, so Mu / Var
+ * may be column ranges of wider buffers), or v_s = var_scalar for every s and e when Var is NULL (a compile-time
+ * variant of the kernels with sigma and the pair sigma hoisted).  With sigma_s = sqrt(v_s), Phi the normal CDF and
+ *   A(m, v) = m erf(m / sqrt(2 v)) + sqrt(2 v / pi) exp(-m^2 / (2 v)):
+ *   pit[e]    = (1/S) sum_s Phi((y[e] - mu_s) / sigma_s)                                  (needs y),
+ *   spread[e] = t2 = (sum_{t<s} A(mu_s - mu_t, v_s + v_t) + sum_s sigma_s / sqrt(pi)) / S^2
+ *             = (1 / (2 S^2)) sum_s sum_t A(mu_s - mu_t, v_s + v_t),
+ *   crps[e]   = (1/S) sum_s A(y[e] - mu_s, v_s) - t2                                      (needs y),
+ *   quantiles[k * ld_q + e] = the root q of (1/S) sum_s Phi((q - mu_s) / sigma_s) = p[k], bisected from
+ *     [min_s, max_s](mu_s + z_p[k] sigma_s), widened by 1e-12 max_s(|mu_s| + |z_p[k]| sigma_s), until no double lies
+ *     strictly between the ends; the end with the smaller |F - p| is returned.  z_p[k] = Phi^-1(p[k]) comes from the
+ *     caller; p and z_p are HOST arrays of nq <= 16 values (passed to the kernel by value), p strictly inside (0, 1).
+ *     A quantile not down to adjacent doubles after 200 steps is NaN and adds 1 to *unconverged (device int32,
+ *     required with nq > 0, never reset here).
+ * Every output is optional (NULL = not computed) and WRITTEN at its E addressed elements only; y (E, contiguous) is
+ * required by pit and crps.  An entry with a non-finite mu_s, or a v_s that is non-finite or <= 0, is NaN in every
+ * output (and not counted in *unconverged); a non-finite y[e] makes pit[e] and crps[e] NaN, spread and quantiles
+ * are still computed; other entries are not affected.  A workgroup serves 8 adjacent entries (64-byte row segments
+ * of Mu / Var).  The S (S - 1) / 2 pair terms of an entry are cut into min(T (T + 1) / 2, 64) slices of tile pairs,
+ * T = ceil(S / 128): a function of S alone.  The slices' partial sums go through `ws` (nmgp_mix_score_workspace_size
+ * bytes; needed for crps / spread only, 0 at S = 1) and are added in slice order, every reduction inside a workgroup
+ * in a fixed order: no floating-point atomics, the same call gives the same bits, and an entry's bits do not
+ * depend on which other entries share the call.  All indexing is 64-bit.  Returns 0 (nothing launched when E == 0),
+ * NMGP_ERR_MIX_ARG before any launch when S is outside 1..2^20, E or nq is negative, nq > 16, E > 8 (2^31 - 1), Mu
+ * is NULL, ld_mu < E, Var is given with ld_var < E or is NULL with a var_scalar that is not finite and positive, pit
+ * or crps is asked for without y, no output is asked for, nq > 0 and z_p, p, quantiles or unconverged is NULL or
+ * ld_q < E, a p[k] is not strictly inside (0, 1), a z_p[k] is not finite, or crps / spread is asked for and the
+ * workspace is missing / too small.                                                                              */
+#define NMGP_ERR_MIX_ARG (-67)
+int64_t nmgp_mix_score_workspace_size(int S, int64_t E);
+int nmgp_mix_score_f64(const double* Mu, int64_t ld_mu, const double* Var, int64_t ld_var, double var_scalar, int S,
+                       int64_t E, const double* y, const double* z_p, const double* p, int nq, double* pit,
+                       double* crps, double* spread, double* quantiles, int64_t ld_q, int32_t* unconverged, void* ws,
+                       int64_t ws_bytes, hipStream_t stream);
+
 /* Whole-step HIP graphs (the reference runs its step eagerly, code/nmgp_dsvi.py:829-854; the build captures
  * noise -> forward -> backward -> Adam once and replays it).  Capture goes straight through the HIP runtime:
  * begin on `stream` (thread-local mode; other streams join through event waits and must join back before
