@@ -250,6 +250,10 @@ _SIGS = {
     "nmgp_mix_score_workspace_size": (c_i64, [c_int, c_i64]),
     "nmgp_mix_score_f64": (c_int, [c_vp, c_i64, c_vp, c_i64, c_dbl, c_int, c_i64, c_vp, c_vp, c_vp, c_int, c_vp, c_vp,
                                    c_vp, c_vp, c_i64, c_vp, c_vp, c_i64, c_vp]),
+    "nmgp_pre_estimate_f64": (c_int, [c_vp, c_i64, c_vp, c_i64, c_vp, c_vp, c_i64, c_int, c_int, c_int, c_int, c_vp,
+                                      c_vp, c_vp, c_vp, c_vp, c_vp, c_vp]),
+    "nmgp_pre_loglik_f64": (c_int, [c_vp, c_i64, c_vp, c_i64, c_vp, c_vp, c_i64, c_int, c_int, c_int, c_int, c_vp,
+                                    c_int, c_vp, c_vp, c_vp, c_vp]),
     "nmgp_counter_add": (c_int, [c_vp, c_i64, c_vp]),
     "nmgp_pbar_reduce_f64": (c_int, [c_vp, c_i64, c_vp, c_i64, c_vp, c_int, c_int, c_int, c_vp]),
     "nmgp_pbar_reduce_f32": (c_int, [c_vp, c_i64, c_vp, c_i64, c_vp, c_int, c_int, c_int, c_vp]),

@@ -1586,5 +1586,91 @@ def mix_score_(Mu, Var_or_float, y=None, qs=(), crps=True, ws=None, out=None):
     return res
 
 
+PRE_MIN_P, PRE_MAX_P, PRE_MAX_D = 3, 32, 128      # csrc/preest.hip kPeMinP, kPeMaxP, kPeMaxD
+PRE_FLAG_ELL_LO, PRE_FLAG_ELL_HI, PRE_FLAG_S_LO, PRE_FLAG_S_HI, PRE_FLAG_JACOBI, PRE_FLAG_DEGENERATE = 1, 2, 4, 8, 16, 32
+
+
+def _pre_args(x, Yrot, mu, z, P):
+    """The checks of the pre-estimation launches that need no device -> (N, D, M, P); ValueError otherwise."""
+    for t, name, nd in ((x, "x", 1), (Yrot, "Yrot", 2), (mu, "mu", 1), (z, "z", 1)):
+        if not torch.is_tensor(t) or t.dtype != torch.float64 or t.dim() != nd:
+            raise ValueError(f"{name} must be a float64 tensor with {nd} dimension(s)")
+        if t.device != x.device:
+            raise ValueError(f"{name} must be on x's device")
+    N, D = Yrot.shape
+    M, P = z.shape[0], int(P)
+    if x.shape[0] != N or mu.shape[0] != D:
+        raise ValueError(f"x must be ({N},) and mu ({D},) for Yrot {tuple(Yrot.shape)}")
+    if not PRE_MIN_P <= P <= PRE_MAX_P:
+        raise ValueError(f"P must lie in {PRE_MIN_P}..{PRE_MAX_P}, got {P}")
+    if not 1 <= D <= PRE_MAX_D:
+        raise ValueError(f"D must lie in 1..{PRE_MAX_D}, got {D}")
+    if N < P:
+        raise ValueError(f"the window needs P = {P} rows, there are {N}")
+    if not (D == 1 or Yrot.stride(1) == 1) or not (N == 1 or Yrot.stride(0) >= D):
+        raise ValueError("Yrot must have unit column stride and a row stride >= D")
+    if (N > 1 and x.stride(0) < 1) or (M > 1 and z.stride(0) < 1):
+        raise ValueError("x and z must have positive strides")
+    return N, D, M, P
+
+
+def _pre_out(out, key, shape, dtype, dev):
+    t = (out or {}).get(key)
+    if t is None:
+        return torch.empty(shape, dtype=dtype, device=dev)
+    if t.dtype != dtype or tuple(t.shape) != tuple(shape) or t.device != dev or not t.is_contiguous():
+        raise ValueError(f"out[{key!r}] must be a contiguous {dtype} {tuple(shape)} tensor on the inputs' device")
+    return t
+
+
+def _pre_common(x, Yrot, mu, z, N, D, M, P):
+    mu = mu.contiguous()
+    return mu, (L.ptr(x), x.stride(0) if N > 1 else 1, L.ptr(Yrot), Yrot.stride(0) if N > 1 else D, L.ptr(mu),
+                L.ptr(z), z.stride(0) if M > 1 else 1, N, D, M, P)
+
+
+def pre_estimate_(x, Yrot, mu, z, P, out=None):
+    """Local stationary fits around the inducing inputs z (csrc/preest.hip): per z_m the P nearest rows of x (N,), the
+    window likelihood with B = V_B diag(mu) V_B^T and Yrot = Y V_B (N, D; a column range of a wider buffer is fine),
+    minimised over (log s, log ell) by the kernel's fixed search.  x and z may be strided views.  Returns a dict of
+    device tensors: "log_ell", "log_s", "nll" (M,) float64, "flags" (M,) int32 (PRE_FLAG_*), "neighbours" (M, P)
+    int32 in ascending row order, "box" (M, 4) the search box (log ell lower, upper, log s lower, upper).  out:
+    contiguous tensors to write into instead, by the same keys.  Argument errors raise ValueError before any device
+    work."""
+    N, D, M, P = _pre_args(x, Yrot, mu, z, P)
+    L.require_device(x, "x")
+    dev, f64, i32 = x.device, torch.float64, torch.int32
+    res = {k: _pre_out(out, k, (M,), f64, dev) for k in ("log_ell", "log_s", "nll")}
+    res["flags"] = _pre_out(out, "flags", (M,), i32, dev)
+    res["neighbours"] = _pre_out(out, "neighbours", (M, P), i32, dev)
+    res["box"] = _pre_out(out, "box", (M, 4), f64, dev)
+    mu, common = _pre_common(x, Yrot, mu, z, N, D, M, P)
+    L.check(L.lib().nmgp_pre_estimate_f64(*common, L.ptr(res["log_ell"]), L.ptr(res["log_s"]), L.ptr(res["nll"]),
+                                          L.ptr(res["flags"]), L.ptr(res["neighbours"]), L.ptr(res["box"]),
+                                          L.stream_handle()), "pre_estimate")
+    return res
+
+
+def pre_loglik_(x, Yrot, mu, z, P, pars, out=None):
+    """The window negative log-likelihoods of pre_estimate_ at the caller's points: pars (M, E, 2) float64 holds
+    (log s, log ell) pairs, the result "nll" is (M, E); "flags" (M,) carries PRE_FLAG_JACOBI / PRE_FLAG_DEGENERATE,
+    "neighbours" (M, P) the windows."""
+    N, D, M, P = _pre_args(x, Yrot, mu, z, P)
+    L.require_device(x, "x")
+    if not torch.is_tensor(pars) or pars.dtype != torch.float64 or pars.dim() != 3 or pars.shape[0] != M \
+            or pars.shape[2] != 2 or pars.device != x.device:
+        raise ValueError(f"pars must be a float64 ({M}, E, 2) tensor on x's device")
+    pars = pars.contiguous()
+    E = pars.shape[1]
+    dev = x.device
+    res = {"nll": _pre_out(out, "nll", (M, E), torch.float64, dev),
+           "flags": _pre_out(out, "flags", (M,), torch.int32, dev),
+           "neighbours": _pre_out(out, "neighbours", (M, P), torch.int32, dev)}
+    mu, common = _pre_common(x, Yrot, mu, z, N, D, M, P)
+    L.check(L.lib().nmgp_pre_loglik_f64(*common, L.ptr(pars), E, L.ptr(res["nll"]), L.ptr(res["flags"]),
+                                        L.ptr(res["neighbours"]), L.stream_handle()), "pre_loglik")
+    return res
+
+
 def counter_add_(counter, inc):
     L.check(L.lib().nmgp_counter_add(ctypes.c_void_p(counter.data_ptr()), int(inc), L.stream_handle()), "counter")

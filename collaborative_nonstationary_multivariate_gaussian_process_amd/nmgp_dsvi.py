@@ -25,7 +25,10 @@ from . import _lib as Lb
 from . import distributed as DD
 from . import hip_ops as H
 from .engine import DsviEngine, use_adam_lower, HYPER_NAMES, PARAM_NAMES, lower_block_ranges, param_layout
+from .pre_nmgp import pre_estimation_partial
 from .utils import TensorType, tridiagonal_jitter  # noqa: F401  (re-exported like the reference)
+
+pre_estimation = pre_estimation_partial      # code/nmgp_dsvi.py:16
 
 F64 = torch.float64
 
@@ -411,6 +414,26 @@ def pre_intialization(M, D, factor=1e-2):
     sqrt_W = np.stack([np.eye(M) for _ in range(D)]) * factor
     sqrt_U = np.stack([np.stack([np.eye(M) for _ in range(D)]) for _ in range(D)]) * factor
     return mu_W, sqrt_v, sqrt_W, sqrt_U
+
+
+def init_from_pre_estimation(v_array, L_tensor, sigma2_err_log_array):
+    """The starting state that pre_estimation's result stands for -> {"mu_v", "mu_U", "sigma2_err_log"}.
+
+    mu_v = v_array: the model's ell_Z = exp(v), and the Gibbs kernel with equal length scales is the RBF kernel of
+    that length scale.  mu_U[i, j, :] = L_tensor[i, j, :] below the diagonal, zero above it and log L_ii ON the
+    diagonal: the model exponentiates the diagonal of its coefficient factor (code/nmgp_dsvi.py:231-233; the
+    reference's commented-out call passed the factor raw).  sigma2_err_log is the median over the windows."""
+    v = np.asarray(v_array, np.float64).reshape(-1)
+    Lt = np.asarray(L_tensor, np.float64)
+    s = np.asarray(sigma2_err_log_array, np.float64).reshape(-1)
+    if Lt.ndim != 3 or Lt.shape[0] != Lt.shape[1] or Lt.shape[2] != v.shape[0] or s.shape != v.shape:
+        raise ValueError(f"expected v (M,), L (D, D, M), sigma2_err_log (M,); got {v.shape}, {Lt.shape}, {s.shape}")
+    D = Lt.shape[0]
+    if not (Lt[np.arange(D), np.arange(D), :] > 0).all():
+        raise ValueError("L_tensor needs a positive diagonal (a Cholesky factor)")
+    mu_U = np.tril(Lt.transpose(2, 0, 1), -1).transpose(1, 2, 0).copy()
+    mu_U[np.arange(D), np.arange(D), :] = np.log(Lt[np.arange(D), np.arange(D), :])
+    return {"mu_v": v.copy(), "mu_U": mu_U, "sigma2_err_log": float(np.median(s))}
 
 
 def vec2list(X, Y, I, dim, device=None):
@@ -833,7 +856,8 @@ def inference(X_train_list, Y_train_list, z, batch_size, dim_outputs, hyperpars=
               mu_v=None, mu_W=None, mu_U=None, sqrt_v=None, sqrt_W=None, sqrt_U=None, lr=0.01, itnum=1000,
               do_stop_criterion=False, seed=22, verbose=False, PATH="model.pt", continuous_training=False,
               show_ELBO=True, save_model=False, X_test_list=None, Y_test_list=None, device=None, noise="torch",
-              use_graph=None, n_elbo_sample=1000, distributed=False, group=None, dtype=F64, check_every=64):
+              use_graph=None, n_elbo_sample=1000, distributed=False, group=None, dtype=F64, check_every=64,
+              pre_estimate=None):
     """code/nmgp_dsvi.py:758-909 on the MI355X.
 
     Returns (model, loss_list, time_list), or (model, loss_list, rmse_test_list, time_list) when
@@ -849,8 +873,20 @@ def inference(X_train_list, Y_train_list, z, batch_size, dim_outputs, hyperpars=
     samples), check_every (noise="device": steps between the host checks of the Cholesky info /
     device status -- the only synchronisations of the loop besides verbose / test / ELBO output).
     A non-positive-definite factor raises torch.linalg.LinAlgError, as the reference's
-    torch.cholesky does.
+    torch.cholesky does.  pre_estimate: None (default) changes nothing; an int P runs pre_estimation_partial
+    with windows of P rows at z when neither mu_v nor mu_U is given -- on the union of the training inputs, the
+    outputs bridged onto it by predict.observed_grid (rows where an output is missing are dropped) -- and starts
+    from init_from_pre_estimation of its result: mu_v, mu_U, and sigma2_err_log unless `hyperpars` sets it or a
+    checkpoint is continued.
     """
+    pre_init = None
+    if pre_estimate is not None and mu_v is None and mu_U is None:
+        from . import predict as _pred0
+        xu = np.unique(np.concatenate([np.asarray(a, np.float64).reshape(-1) for a in X_train_list]))
+        Y_grid = _pred0.observed_grid(X_train_list, Y_train_list, xu)
+        pre_init = init_from_pre_estimation(*pre_estimation_partial(xu, Y_grid, np.asarray(z, np.float64).reshape(-1),
+                                                                    P=int(pre_estimate), device=device))
+        mu_v, mu_U = pre_init["mu_v"], pre_init["mu_U"]
     rank, world = DD.world_info(group) if distributed else (0, 1)
     if use_graph is None:
         # device noise: one graph per step; data parallel on the graph path: gradient graph, one all-reduce,
@@ -869,6 +905,8 @@ def inference(X_train_list, Y_train_list, z, batch_size, dim_outputs, hyperpars=
                  minibatch_size=batch_size, mu_v=mu_v, mu_W=mu_W, mu_U=mu_U, sqrt_v=sqrt_v, sqrt_W=sqrt_W,
                  sqrt_U=sqrt_U, seed=seed, device=device, noise=noise, dtype=dtype)
     opt_state = {}
+    if pre_init is not None and not continuous_training and "sigma2_err_log" not in (hyperpars or {}):
+        model.sigma2_err_log.data.fill_(pre_init["sigma2_err_log"])
     _apply_hyperpars(model, hyperpars, fix_hyperpars, continuous_training, PATH, opt_state)
     trainer = DsviTrainer(model, lr)
     trainer.load_optimizer_state(opt_state)

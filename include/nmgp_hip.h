@@ -920,6 +920,35 @@ int nmgp_mix_score_f64(const double* Mu, int64_t ld_mu, const double* Var, int64
                        double* crps, double* spread, double* quantiles, int64_t ld_q, int32_t* unconverged, void* ws,
                        int64_t ws_bytes, hipStream_t stream);
 
+/* Local stationary fits around the inducing points, fused (csrc/preest.hip): the reference's pre_estimation_partial
+ * (code/pre_nmgp.py:102-125), one workgroup per inducing point, fp64, no matrix cores.  x (N inputs of the complete
+ * rows, element stride x_stride >= 1), Yrot = Y V_B (N rows of D, row stride ld_y >= D), mu (D, the eigenvalues of
+ * B = Y^T Y / (N - 1) = V_B diag(mu) V_B^T), z (M inducing inputs, element stride z_stride >= 1).  Window m holds the
+ * P rows with the smallest |x_n - z_m| (ties to the lower row), written in ascending row order to
+ * neighbours[m * P + p] (optional).  Its likelihood is vec(Y_loc) ~ N(0, K(ell) (x) B + s I), evaluated as
+ *   nll = 1/2 sum_pd [log G_pd + E_pd / G_pd] + 1/2 P D log 2 pi,  G_pd = lam_p mu_d + s,  E = (V_K^T Yrot_loc)^2,
+ * K = V_K diag(lam) V_K^T the RBF kernel of the window inputs (divide by ell, then difference; ell < 1e-8 clamped).
+ * nmgp_pre_estimate_f64 minimises it over the box log ell in [log(delta / 4), log(16 span)] (delta the smallest
+ * positive gap of the sorted window inputs, span their range), log s in log(mean mu) + [-14, 2], by the fixed search
+ * described in csrc/preest.hip, and writes log_ell[m], log_s[m], nll[m], flags[m] and (optional) box[m * 4 + 0..3] =
+ * the four box ends in that order.  Flag bits: 1 / 2 log ell at its lower / upper end, 4 / 8 log s at its lower /
+ * upper end, 16 a Jacobi solve did not converge in 30 sweeps, 32 degenerate window (span 0 or fewer than P finite
+ * inputs: the results are NaN).  nmgp_pre_loglik_f64 evaluates nll[m * E + e] at the caller's pairs
+ * pars[(m * E + e) * 2 + 0 / 1] = (log s, log ell) on the same windows (flags: bits 16 and 32 only).  Only the
+ * addressed elements are written.  Every loop is bounded and every sum has a fixed order: the same call gives the
+ * same bits, and a window's bits do not depend on the other windows of the call.  Both return 0 (nothing launched at
+ * M == 0) and NMGP_ERR_PREEST_ARG before any launch when P is outside 3..32, D outside 1..128, N < P, M or E is
+ * negative, a required pointer is NULL, a stride is below 1, ld_y < D, or an element offset ((N - 1) x_stride,
+ * N ld_y, (M - 1) z_stride, M P) passes 2^31 - 1.                                                              */
+#define NMGP_ERR_PREEST_ARG (-68)
+int nmgp_pre_estimate_f64(const double* x, int64_t x_stride, const double* Yrot, int64_t ld_y, const double* mu,
+                          const double* z, int64_t z_stride, int N, int D, int M, int P, double* log_ell,
+                          double* log_s, double* nll, int32_t* flags, int32_t* neighbours, double* box,
+                          hipStream_t stream);
+int nmgp_pre_loglik_f64(const double* x, int64_t x_stride, const double* Yrot, int64_t ld_y, const double* mu,
+                        const double* z, int64_t z_stride, int N, int D, int M, int P, const double* pars, int E,
+                        double* nll, int32_t* flags, int32_t* neighbours, hipStream_t stream);
+
 /* Whole-step HIP graphs (the reference runs its step eagerly, code/nmgp_dsvi.py:829-854; the build captures
  * noise -> forward -> backward -> Adam once and replays it).  Capture goes straight through the HIP runtime:
  * begin on `stream` (thread-local mode; other streams join through event waits and must join back before
