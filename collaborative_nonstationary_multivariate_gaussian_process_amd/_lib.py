@@ -254,6 +254,13 @@ _SIGS = {
                                       c_vp, c_vp, c_vp, c_vp, c_vp, c_vp]),
     "nmgp_pre_loglik_f64": (c_int, [c_vp, c_i64, c_vp, c_i64, c_vp, c_vp, c_i64, c_int, c_int, c_int, c_int, c_vp,
                                     c_int, c_vp, c_vp, c_vp, c_vp]),
+    "nmgp_pre_estimate_windows_f64": (c_int, [c_vp, c_vp, c_vp, c_int, c_int, c_int, c_vp, c_vp, c_vp, c_vp, c_vp,
+                                              c_vp, c_vp]),
+    "nmgp_pre_loglik_windows_f64": (c_int, [c_vp, c_vp, c_vp, c_int, c_int, c_int, c_vp, c_vp, c_int, c_vp, c_vp,
+                                            c_vp]),
+    "nmgp_pre_local_factor_f64": (c_int, [c_vp, c_i64, c_vp, c_i64, c_vp, c_i64, c_vp, c_i64, c_int, c_int, c_int,
+                                          c_int, c_int, c_int, c_dbl, c_dbl, c_vp, c_vp, c_vp, c_vp, c_vp, c_vp,
+                                          c_vp, c_vp]),
     "nmgp_counter_add": (c_int, [c_vp, c_i64, c_vp]),
     "nmgp_pbar_reduce_f64": (c_int, [c_vp, c_i64, c_vp, c_i64, c_vp, c_int, c_int, c_int, c_vp]),
     "nmgp_pbar_reduce_f32": (c_int, [c_vp, c_i64, c_vp, c_i64, c_vp, c_int, c_int, c_int, c_vp]),

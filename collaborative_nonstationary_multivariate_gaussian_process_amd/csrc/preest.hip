@@ -133,6 +133,18 @@ __device__ void pe_window(PeShared& s, double* Yl, const double* __restrict__ x,
   __syncthreads();
 }
 
+// The window handed over as data (the local-factor form): xs (P), Yrot_loc (P x D) and mu (D) of this window; a
+// window that arrives flagged (carry != 0) is not fitted.
+__device__ void pe_window_data(PeShared& s, double* Yl, const double* __restrict__ xs, const double* __restrict__ Yrot_loc,
+                               const double* __restrict__ mu, int D, int P, int carry) {
+  const int tid = threadIdx.x;
+  if (tid == 0) s.degenerate = carry != 0 ? 1 : 0;
+  if (tid < P) s.xs[tid] = xs[tid];
+  for (int d = tid; d < D; d += kPeThreads) s.mu[d] = mu[d];
+  for (int e = tid; e < P * D; e += kPeThreads) Yl[e] = Yrot_loc[e];
+  __syncthreads();
+}
+
 // Box of the search into s.box; sets s.degenerate at span 0 (thread 0 works, everybody sees the result).
 __device__ void pe_box(PeShared& s, int P, int D) {
   if (threadIdx.x == 0 && s.degenerate == 0) {
@@ -334,20 +346,29 @@ __device__ inline void pe_prof_at(PeShared& s, const double* Yl, double* Eb, dou
   pe_profile(s, Eb, G0, P * D, s.box[2], s.box[3], t, f);
 }
 
-// MODE 0: the search.  MODE 1: nll at the caller's n_eval (log s, log ell) pairs per window.
-template <int MODE>
+// MODE 0: the search.  MODE 1: nll at the caller's n_eval (log s, log ell) pairs per window.  WIN: the windows come as
+// data, x = xs (M, P), Yrot = Yrot_loc (M, P, D), mu (M, D); z, the strides and N are not read; win_flags (optional):
+// a window with a non-zero entry is not fitted, its results are NaN and its flags that entry.
+template <int MODE, bool WIN = false>
 __global__ __launch_bounds__(kPeThreads) void preest_kernel(
     const double* __restrict__ x, int64_t x_stride, const double* __restrict__ Yrot, int64_t ld_y,
     const double* __restrict__ mu, const double* __restrict__ z, int64_t z_stride, int N, int D, int P,
     const double* __restrict__ pars, int n_eval, double* __restrict__ out_ell, double* __restrict__ out_s,
-    double* __restrict__ out_nll, int* __restrict__ out_flags, int* __restrict__ out_nbr, double* __restrict__ out_box) {
+    double* __restrict__ out_nll, int* __restrict__ out_flags, int* __restrict__ out_nbr, double* __restrict__ out_box,
+    const int* __restrict__ win_flags) {
   extern __shared__ __attribute__((aligned(16))) double pe_smem[];
   __shared__ PeShared s;
   double *Yl = pe_smem, *Eb = Yl + P * D, *G0 = Eb + P * D;
   const int tid = threadIdx.x, mwin = blockIdx.x, PD = P * D;
   const double nan = __builtin_nan("");
   if (tid == 0) s.jacobi_bad = 0;
-  pe_window(s, Yl, x, x_stride, Yrot, ld_y, mu, z[(int64_t)mwin * z_stride], N, D, P);
+  int bad_flag = kPeFlagDegenerate;
+  if constexpr (WIN) {
+    const int carry = win_flags ? win_flags[mwin] : 0;
+    if (carry != 0) bad_flag = carry;
+    pe_window_data(s, Yl, x + (int64_t)mwin * P, Yrot + (int64_t)mwin * PD, mu + (int64_t)mwin * D, D, P, carry);
+  } else
+    pe_window(s, Yl, x, x_stride, Yrot, ld_y, mu, z[(int64_t)mwin * z_stride], N, D, P);
   if (out_nbr && tid < P) out_nbr[(int64_t)mwin * P + tid] = s.idx[tid];
 
   if (MODE == 1) {
@@ -363,7 +384,7 @@ __global__ __launch_bounds__(kPeThreads) void preest_kernel(
     }
     __syncthreads();
     if (tid == 0)
-      out_flags[mwin] = (bad ? kPeFlagDegenerate : 0) | (s.jacobi_bad ? kPeFlagJacobi : 0);
+      out_flags[mwin] = (bad ? bad_flag : 0) | (s.jacobi_bad ? kPeFlagJacobi : 0);
     return;
   }
 
@@ -373,7 +394,7 @@ __global__ __launch_bounds__(kPeThreads) void preest_kernel(
       out_ell[mwin] = nan;
       out_s[mwin] = nan;
       out_nll[mwin] = nan;
-      out_flags[mwin] = kPeFlagDegenerate;
+      out_flags[mwin] = bad_flag;
     }
     if (out_box && tid < 4) out_box[(int64_t)mwin * 4 + tid] = nan;
     return;
@@ -450,11 +471,11 @@ static bool pe_args_ok(const void* x, int64_t x_stride, const void* Yrot, int64_
   return true;
 }
 
-template <int MODE, class... Args>
+template <int MODE, bool WIN = false, class... Args>
 static int pe_launch(int M, int P, int D, hipStream_t stream, Args... args) {
-  allow_dynamic_lds<preest_kernel<MODE>>((size_t)3 * kPeMaxP * kPeMaxD * sizeof(double));
+  allow_dynamic_lds<preest_kernel<MODE, WIN>>((size_t)3 * kPeMaxP * kPeMaxD * sizeof(double));
   const size_t smem = (size_t)3 * P * D * sizeof(double);
-  hipLaunchKernelGGL(preest_kernel<MODE>, dim3((unsigned)M), dim3(kPeThreads), smem, stream, args...);
+  hipLaunchKernelGGL((preest_kernel<MODE, WIN>), dim3((unsigned)M), dim3(kPeThreads), smem, stream, args...);
   NMGP_CHECK_LAUNCH();
   return NMGP_OK;
 }
@@ -473,7 +494,7 @@ int nmgp_pre_estimate_f64(const double* x, int64_t x_stride, const double* Yrot,
   if (!log_ell || !log_s || !nll || !flags) return NMGP_ERR_PREEST_ARG;
   if (M == 0) return NMGP_OK;
   return pe_launch<0>(M, P, D, stream, x, x_stride, Yrot, ld_y, mu, z, z_stride, N, D, P, (const double*)nullptr, 0,
-                      log_ell, log_s, nll, (int*)flags, (int*)neighbours, box);
+                      log_ell, log_s, nll, (int*)flags, (int*)neighbours, box, (const int*)nullptr);
 }
 
 int nmgp_pre_loglik_f64(const double* x, int64_t x_stride, const double* Yrot, int64_t ld_y, const double* mu,
@@ -483,7 +504,36 @@ int nmgp_pre_loglik_f64(const double* x, int64_t x_stride, const double* Yrot, i
   if (E < 0 || (int64_t)M * E > 0x3fffffffLL || !flags || (E > 0 && (!pars || !nll))) return NMGP_ERR_PREEST_ARG;
   if (M == 0) return NMGP_OK;
   return pe_launch<1>(M, P, D, stream, x, x_stride, Yrot, ld_y, mu, z, z_stride, N, D, P, pars, E,
-                      (double*)nullptr, (double*)nullptr, nll, (int*)flags, (int*)neighbours, (double*)nullptr);
+                      (double*)nullptr, (double*)nullptr, nll, (int*)flags, (int*)neighbours, (double*)nullptr,
+                      (const int*)nullptr);
+}
+
+static bool pe_windows_ok(const void* xs, const void* Yrot_loc, const void* mu, int M, int D, int P) {
+  if (P < kPeMinP || P > kPeMaxP || D < 1 || D > kPeMaxD || M < 0) return false;
+  if (!xs || !Yrot_loc || !mu) return false;
+  return (int64_t)M * P * D <= 0x7fffffffLL;
+}
+
+int nmgp_pre_estimate_windows_f64(const double* xs, const double* Yrot_loc, const double* mu, int M, int D, int P,
+                                  const int32_t* window_flags, double* log_ell, double* log_s, double* nll,
+                                  int32_t* flags, double* box, hipStream_t stream) {
+  if (!pe_windows_ok(xs, Yrot_loc, mu, M, D, P)) return NMGP_ERR_PREEST_ARG;
+  if (!log_ell || !log_s || !nll || !flags) return NMGP_ERR_PREEST_ARG;
+  if (M == 0) return NMGP_OK;
+  return pe_launch<0, true>(M, P, D, stream, xs, (int64_t)1, Yrot_loc, (int64_t)D, mu, (const double*)nullptr,
+                            (int64_t)1, P, D, P, (const double*)nullptr, 0, log_ell, log_s, nll, (int*)flags,
+                            (int*)nullptr, box, (const int*)window_flags);
+}
+
+int nmgp_pre_loglik_windows_f64(const double* xs, const double* Yrot_loc, const double* mu, int M, int D, int P,
+                                const int32_t* window_flags, const double* pars, int E, double* nll, int32_t* flags,
+                                hipStream_t stream) {
+  if (!pe_windows_ok(xs, Yrot_loc, mu, M, D, P)) return NMGP_ERR_PREEST_ARG;
+  if (E < 0 || (int64_t)M * E > 0x3fffffffLL || !flags || (E > 0 && (!pars || !nll))) return NMGP_ERR_PREEST_ARG;
+  if (M == 0) return NMGP_OK;
+  return pe_launch<1, true>(M, P, D, stream, xs, (int64_t)1, Yrot_loc, (int64_t)D, mu, (const double*)nullptr,
+                            (int64_t)1, P, D, P, pars, E, (double*)nullptr, (double*)nullptr, nll, (int*)flags,
+                            (int*)nullptr, (double*)nullptr, (const int*)window_flags);
 }
 
 }  // extern "C"

@@ -1672,5 +1672,125 @@ def pre_loglik_(x, Yrot, mu, z, P, pars, out=None):
     return res
 
 
+PRE_MAX_COV_ROWS = 1024                           # csrc/prelocal.hip kPlMaxCov
+PRE_FLAG_FACTOR = 64                              # include/nmgp_hip.h NMGP_PRE_FLAG_FACTOR
+
+
+def _pre_local_args(x, Y, B, z, P, cov_rows, w, alpha, holdout):
+    """The checks of the local-factor launch that need no device -> (N, D, M, P, Pc, w, alpha, holdout)."""
+    for t, name, nd in ((x, "x", 1), (Y, "Y", 2), (B, "B", 2), (z, "z", 1)):
+        if not torch.is_tensor(t) or t.dtype != torch.float64 or t.dim() != nd:
+            raise ValueError(f"{name} must be a float64 tensor with {nd} dimension(s)")
+        if t.device != x.device:
+            raise ValueError(f"{name} must be on x's device")
+    N, D = Y.shape
+    M, P, Pc, holdout = z.shape[0], int(P), int(cov_rows), bool(holdout)
+    w, alpha = float(w), float(alpha)
+    if x.shape[0] != N or tuple(B.shape) != (D, D):
+        raise ValueError(f"x must be ({N},) and B ({D}, {D}) for Y {tuple(Y.shape)}")
+    if not PRE_MIN_P <= P <= PRE_MAX_P:
+        raise ValueError(f"P must lie in {PRE_MIN_P}..{PRE_MAX_P}, got {P}")
+    if not 1 <= D <= PRE_MAX_D:
+        raise ValueError(f"D must lie in 1..{PRE_MAX_D}, got {D}")
+    if not P <= Pc <= PRE_MAX_COV_ROWS:
+        raise ValueError(f"cov_rows must lie in P = {P}..{PRE_MAX_COV_ROWS}, got {Pc}")
+    if P * holdout + Pc > N:
+        raise ValueError(f"the windows need {'P + ' if holdout else ''}cov_rows = {P * holdout + Pc} rows, there are {N}")
+    if not 0.0 <= alpha <= 1.0:
+        raise ValueError(f"alpha must lie in [0, 1], got {alpha}")
+    if not (w >= 0.0 and w < float("inf")):
+        raise ValueError(f"w must be finite and non-negative, got {w}")
+    for t, name in ((Y, "Y"), (B, "B")):
+        if not (D == 1 or t.stride(1) == 1) or not (t.shape[0] == 1 or t.stride(0) >= D):
+            raise ValueError(f"{name} must have unit column stride and a row stride >= D")
+    if (N > 1 and x.stride(0) < 1) or (M > 1 and z.stride(0) < 1):
+        raise ValueError("x and z must have positive strides")
+    return N, D, M, P, Pc, w, alpha, holdout
+
+
+def pre_local_factor_(x, Y, B, z, P, cov_rows, w, alpha, holdout, out=None):
+    """Local coefficient factors around the inducing inputs z (csrc/prelocal.hip).  Per z_m the rows of x (N,) are
+    ordered by (|x_n - z_m|, n); the fit window is the first P rows, the covariance window the next cov_rows rows
+    (holdout) or the first cov_rows rows.  "B_local" (M, D, D) = w Y_w^T Y_w + alpha B over the covariance rows Y_w of
+    Y (N, D), B (D, D) the global matrix; "L" (M, D, D) its lower Cholesky factors; "neighbours" (M, P) and
+    "cov_neighbours" (M, cov_rows) int32 in ascending row order; "xs" (M, P) and "Yloc" (M, P, D) the fit rows;
+    "flags" (M,) int32: PRE_FLAG_DEGENERATE (too few finite inputs) or PRE_FLAG_FACTOR (B_local[m] not positive
+    definite: L[m] is NaN).  x and z may be strided views, Y and B column ranges of wider buffers.  out: contiguous
+    tensors to write into instead, by the same keys.  Argument errors raise ValueError before any device work."""
+    N, D, M, P, Pc, w, alpha, holdout = _pre_local_args(x, Y, B, z, P, cov_rows, w, alpha, holdout)
+    L.require_device(x, "x")
+    dev, f64, i32 = x.device, torch.float64, torch.int32
+    res = {"B_local": _pre_out(out, "B_local", (M, D, D), f64, dev), "L": _pre_out(out, "L", (M, D, D), f64, dev),
+           "neighbours": _pre_out(out, "neighbours", (M, P), i32, dev),
+           "cov_neighbours": _pre_out(out, "cov_neighbours", (M, Pc), i32, dev),
+           "xs": _pre_out(out, "xs", (M, P), f64, dev), "Yloc": _pre_out(out, "Yloc", (M, P, D), f64, dev),
+           "flags": _pre_out(out, "flags", (M,), i32, dev)}
+    L.check(L.lib().nmgp_pre_local_factor_f64(
+        L.ptr(x), x.stride(0) if N > 1 else 1, L.ptr(Y), Y.stride(0) if N > 1 else D, L.ptr(B),
+        B.stride(0) if D > 1 else D, L.ptr(z), z.stride(0) if M > 1 else 1, N, D, M, P, Pc, int(holdout), w, alpha,
+        L.ptr(res["B_local"]), L.ptr(res["L"]), L.ptr(res["neighbours"]), L.ptr(res["cov_neighbours"]),
+        L.ptr(res["xs"]), L.ptr(res["Yloc"]), L.ptr(res["flags"]), L.stream_handle()), "pre_local_factor")
+    return res
+
+
+def _pre_window_args(xs, Yrot_loc, mu, flags=None):
+    for t, name, nd in ((xs, "xs", 2), (Yrot_loc, "Yrot_loc", 3), (mu, "mu", 2)):
+        if not torch.is_tensor(t) or t.dtype != torch.float64 or t.dim() != nd:
+            raise ValueError(f"{name} must be a float64 tensor with {nd} dimension(s)")
+        if t.device != xs.device:
+            raise ValueError(f"{name} must be on xs's device")
+    M, P, D = Yrot_loc.shape
+    if tuple(xs.shape) != (M, P) or tuple(mu.shape) != (M, D):
+        raise ValueError(f"xs must be ({M}, {P}) and mu ({M}, {D}) for Yrot_loc {tuple(Yrot_loc.shape)}")
+    if not PRE_MIN_P <= P <= PRE_MAX_P:
+        raise ValueError(f"P must lie in {PRE_MIN_P}..{PRE_MAX_P}, got {P}")
+    if not 1 <= D <= PRE_MAX_D:
+        raise ValueError(f"D must lie in 1..{PRE_MAX_D}, got {D}")
+    if flags is not None and (not torch.is_tensor(flags) or flags.dtype != torch.int32 or tuple(flags.shape) != (M,)
+                              or flags.device != xs.device):
+        raise ValueError(f"flags must be an int32 ({M},) tensor on xs's device")
+    return M, P, D
+
+
+def pre_estimate_windows_(xs, Yrot_loc, mu, out=None, flags=None):
+    """The search of pre_estimate_ on windows given as data: xs (M, P) the window inputs, Yrot_loc (M, P, D) =
+    Y_loc V_m and mu (M, D) the eigenvalues of the window's own B_m = V_m diag(mu_m) V_m^T.  Returns "log_ell",
+    "log_s", "nll" (M,), "flags" (M,) int32 and "box" (M, 4) as pre_estimate_ does.  flags (optional, the "flags" of pre_local_factor_):
+    a window with a non-zero entry is not fitted, its results are NaN and its flags that entry."""
+    M, P, D = _pre_window_args(xs, Yrot_loc, mu, flags)
+    flags = None if flags is None else flags.contiguous()
+    L.require_device(xs, "xs")
+    xs, Yrot_loc, mu = xs.contiguous(), Yrot_loc.contiguous(), mu.contiguous()
+    dev, f64 = xs.device, torch.float64
+    res = {k: _pre_out(out, k, (M,), f64, dev) for k in ("log_ell", "log_s", "nll")}
+    res["flags"] = _pre_out(out, "flags", (M,), torch.int32, dev)
+    res["box"] = _pre_out(out, "box", (M, 4), f64, dev)
+    L.check(L.lib().nmgp_pre_estimate_windows_f64(
+        L.ptr(xs), L.ptr(Yrot_loc), L.ptr(mu), M, D, P, L.ptr(flags), L.ptr(res["log_ell"]), L.ptr(res["log_s"]),
+        L.ptr(res["nll"]), L.ptr(res["flags"]), L.ptr(res["box"]), L.stream_handle()), "pre_estimate_windows")
+    return res
+
+
+def pre_loglik_windows_(xs, Yrot_loc, mu, pars, out=None, flags=None):
+    """The window negative log-likelihoods of pre_estimate_windows_ at the caller's points: pars (M, E, 2) float64
+    holds (log s, log ell) pairs; "nll" is (M, E), "flags" (M,) carries PRE_FLAG_JACOBI and the entries of the
+    optional incoming flags, whose windows are NaN."""
+    M, P, D = _pre_window_args(xs, Yrot_loc, mu, flags)
+    flags = None if flags is None else flags.contiguous()
+    L.require_device(xs, "xs")
+    if not torch.is_tensor(pars) or pars.dtype != torch.float64 or pars.dim() != 3 or pars.shape[0] != M \
+            or pars.shape[2] != 2 or pars.device != xs.device:
+        raise ValueError(f"pars must be a float64 ({M}, E, 2) tensor on xs's device")
+    xs, Yrot_loc, mu, pars = xs.contiguous(), Yrot_loc.contiguous(), mu.contiguous(), pars.contiguous()
+    E = pars.shape[1]
+    res = {"nll": _pre_out(out, "nll", (M, E), torch.float64, xs.device),
+           "flags": _pre_out(out, "flags", (M,), torch.int32, xs.device)}
+    L.check(L.lib().nmgp_pre_loglik_windows_f64(L.ptr(xs), L.ptr(Yrot_loc), L.ptr(mu), M, D, P, L.ptr(flags),
+                                                L.ptr(pars), E,
+                                                L.ptr(res["nll"]), L.ptr(res["flags"]), L.stream_handle()),
+            "pre_loglik_windows")
+    return res
+
+
 def counter_add_(counter, inc):
     L.check(L.lib().nmgp_counter_add(ctypes.c_void_p(counter.data_ptr()), int(inc), L.stream_handle()), "counter")

@@ -25,7 +25,7 @@ from . import _lib as Lb
 from . import distributed as DD
 from . import hip_ops as H
 from .engine import DsviEngine, use_adam_lower, HYPER_NAMES, PARAM_NAMES, lower_block_ranges, param_layout
-from .pre_nmgp import pre_estimation_partial
+from .pre_nmgp import pre_estimation_local, pre_estimation_partial
 from .utils import TensorType, tridiagonal_jitter  # noqa: F401  (re-exported like the reference)
 
 pre_estimation = pre_estimation_partial      # code/nmgp_dsvi.py:16
@@ -877,15 +877,24 @@ def inference(X_train_list, Y_train_list, z, batch_size, dim_outputs, hyperpars=
     with windows of P rows at z when neither mu_v nor mu_U is given -- on the union of the training inputs, the
     outputs bridged onto it by predict.observed_grid (rows where an output is missing are dropped) -- and starts
     from init_from_pre_estimation of its result: mu_v, mu_U, and sigma2_err_log unless `hyperpars` sets it or a
-    checkpoint is continued.
+    checkpoint is continued.  A dict {"cov_rows", and optionally "P", "shrink", "holdout"} runs
+    pre_estimation_local instead: mu_U then starts from the local factors, one per inducing point.
     """
     pre_init = None
     if pre_estimate is not None and mu_v is None and mu_U is None:
         from . import predict as _pred0
         xu = np.unique(np.concatenate([np.asarray(a, np.float64).reshape(-1) for a in X_train_list]))
         Y_grid = _pred0.observed_grid(X_train_list, Y_train_list, xu)
-        pre_init = init_from_pre_estimation(*pre_estimation_partial(xu, Y_grid, np.asarray(z, np.float64).reshape(-1),
-                                                                    P=int(pre_estimate), device=device))
+        zp = np.asarray(z, np.float64).reshape(-1)
+        if isinstance(pre_estimate, dict):
+            unknown = set(pre_estimate) - {"P", "cov_rows", "shrink", "holdout"}
+            if unknown or "cov_rows" not in pre_estimate:
+                raise ValueError("pre_estimate as a dict takes 'cov_rows' and optionally 'P', 'shrink', 'holdout'; "
+                                 f"got {sorted(pre_estimate)}")
+            pre_init = init_from_pre_estimation(*pre_estimation_local(xu, Y_grid, zp, device=device, **pre_estimate))
+        else:
+            pre_init = init_from_pre_estimation(*pre_estimation_partial(xu, Y_grid, zp, P=int(pre_estimate),
+                                                                        device=device))
         mu_v, mu_U = pre_init["mu_v"], pre_init["mu_U"]
     rank, world = DD.world_info(group) if distributed else (0, 1)
     if use_graph is None:

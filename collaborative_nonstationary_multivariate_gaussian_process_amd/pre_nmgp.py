@@ -35,12 +35,34 @@ def _spectral_data(B_dev, Y_dev):
     return mu, H.matmul(Y_dev, VB)
 
 
-def pre_estimate(x, Y, z, P=10, device=None):
+def _local_plan(N, D, P, cov_rows, shrink, holdout):
+    """The checks of the local run that need no device -> (Pc, w, alpha, holdout), w and alpha the doubles the kernel
+    evaluates B_m = w Y_w^T Y_w + alpha B with."""
+    Pc, holdout = int(cov_rows), bool(holdout)
+    if not P <= Pc <= H.PRE_MAX_COV_ROWS:
+        raise ValueError(f"cov_rows must lie in P = {P}..{H.PRE_MAX_COV_ROWS}, got {Pc}")
+    if P * holdout + Pc > N:
+        raise ValueError(f"{N} complete rows, fewer than the {'P + ' if holdout else ''}cov_rows = "
+                         f"{P * holdout + Pc} the windows need")
+    alpha = D / (D + Pc - 1.0) if shrink is None else float(shrink)       # B counts as D pseudo-rows
+    if not 0.0 <= alpha <= 1.0:
+        raise ValueError(f"shrink must lie in [0, 1], got {shrink}")
+    return Pc, (1.0 - alpha) / (Pc - 1.0), alpha, holdout
+
+
+def pre_estimate(x, Y, z, P=10, device=None, cov_rows=None, shrink=None, holdout=True):
     """The run behind pre_estimation_partial as a dict: "v_array" (M,) = log ell, "L_tensor" (D, D, M),
     "sigma2_err_log_array" (M,) = log s, "nll" (M,) the windows' minimal negative log-likelihoods, "flags" (M,) int32
     (hip_ops.PRE_FLAG_*: 1 / 2 log ell at the lower / upper edge of its box, 4 / 8 log s at its lower / upper edge),
     "neighbours" (M, P) int32 rows of the complete-row arrays in ascending order, "B" (D, D), all numpy, and "box"
-    (M, 4).  Raises as pre_estimation_partial does."""
+    (M, 4).  Raises as pre_estimation_partial does.
+
+    cov_rows = Pc switches to the local run behind pre_estimation_local (csrc/prelocal.hip): per inducing point
+    B_m = (1 - alpha) Y_w^T Y_w / (Pc - 1) + alpha B over its covariance window Y_w -- the Pc rows that follow the P
+    fit rows in the order by (|x_n - z_m|, n) (holdout, the default), or the first Pc rows of it -- alpha = shrink, or
+    D / (D + Pc - 1) for None; "L_tensor" then holds chol(B_m) and the fit uses B_m in place of B.  The dict adds
+    "B_local" (M, D, D), "cov_neighbours" (M, Pc), "shrink" (the alpha used) and "holdout".  A B_m that is not
+    positive definite raises numpy.linalg.LinAlgError naming the z indices."""
     x = np.asarray(x, np.float64).reshape(-1)
     Y = np.asarray(Y, np.float64)
     z = np.asarray(z, np.float64).reshape(-1)
@@ -56,10 +78,13 @@ def pre_estimate(x, Y, z, P=10, device=None):
         raise ValueError(f"{N} complete rows, fewer than the P = {P} a window needs")
     if not 1 <= D <= H.PRE_MAX_D:
         raise ValueError(f"D must lie in 1..{H.PRE_MAX_D}, got {D}")
+    plan = None if cov_rows is None else _local_plan(N, D, P, cov_rows, shrink, holdout)
     dev = _device(device)
     Yd = torch.from_numpy(np.ascontiguousarray(Y)).to(dev)
     B = H.matmul(Yd, Yd, transA=True, alpha=1.0 / (N - 1))
     B = 0.5 * (B + B.T)                       # exactly symmetric, whatever order the GEMM summed its tiles in
+    if plan is not None:
+        return _pre_estimate_local(x, Yd, B, z, P, plan, dev)
     Lf = B.clone()
     info = H.potrf_(Lf)
     if int(info.reshape(-1)[0].item()) != 0:
@@ -81,6 +106,52 @@ def pre_estimate(x, Y, z, P=10, device=None):
             "neighbours": out["neighbours"], "B": B.cpu().numpy(), "box": out["box"]}
 
 
+def _pre_estimate_local(x, Yd, B, z, P, plan, dev):
+    """The local run on the complete rows: the factor launch, the windows' eigenbases (existing batched Jacobi and
+    GEMM, on the P fit rows only), the search on the windows."""
+    Pc, w, alpha, holdout = plan
+    fac = H.pre_local_factor_(torch.from_numpy(x).to(dev), Yd, B, torch.from_numpy(z).to(dev), P, Pc, w, alpha, holdout)
+    fflags = fac["flags"].cpu().numpy()
+    bad = _flag_list(fflags, H.PRE_FLAG_DEGENERATE)
+    if bad:
+        raise ValueError(f"degenerate windows (fewer than {P * holdout + Pc} finite inputs) at z index {bad}")
+    bad = _flag_list(fflags, H.PRE_FLAG_FACTOR)
+    if bad:
+        raise np.linalg.LinAlgError(f"the local matrix is not positive definite at z index {bad}")
+    mu, V = H.syevj(fac["B_local"])
+    res = H.pre_estimate_windows_(fac["xs"], H.bmm(fac["Yloc"], V), mu)
+    out = {k: v.cpu().numpy() for k, v in res.items()}
+    flags = out["flags"]
+    bad = _flag_list(flags, H.PRE_FLAG_DEGENERATE)
+    if bad:
+        raise ValueError(f"degenerate windows (all inputs equal, or fewer than P finite inputs) at z index {bad}")
+    bad = _flag_list(flags, H.PRE_FLAG_JACOBI)
+    if bad:
+        raise RuntimeError(f"the Jacobi eigensolver did not converge in the windows at z index {bad}")
+    return {"v_array": out["log_ell"], "L_tensor": np.ascontiguousarray(fac["L"].permute(1, 2, 0).cpu().numpy()),
+            "sigma2_err_log_array": out["log_s"], "nll": out["nll"], "flags": flags,
+            "neighbours": fac["neighbours"].cpu().numpy(), "B": B.cpu().numpy(), "box": out["box"],
+            "B_local": fac["B_local"].cpu().numpy(), "cov_neighbours": fac["cov_neighbours"].cpu().numpy(),
+            "shrink": alpha, "holdout": holdout}
+
+
+def pre_estimation_local(x, Y, z, P=10, cov_rows=40, shrink=None, holdout=True, device=None):
+    """What code/pre_nmgp.py:64-100 (pre_estimation_all) set out to return and never did: (v_array (M,), L_tensor
+    (D, D, M), sigma2_err_log_array (M,)) with a coefficient factor of its own per inducing point.
+
+    L_tensor[:, :, m] = chol((1 - alpha) Y_w^T Y_w / (cov_rows - 1) + alpha Y^T Y / (N - 1)) over the covariance window
+    Y_w of z_m, uncentred as the reference's est_L (:71); v_array[m] and sigma2_err_log_array[m] minimise the
+    likelihood of the P fit rows under that matrix.  holdout (default) keeps the fit rows out of the covariance window:
+    rows that are iid under a covariance estimated from themselves drive the fit to ell -> 0 and s to the lower edge
+    of its box once D is not small against cov_rows.  shrink = alpha in [0, 1]; None counts the global matrix as D
+    pseudo-rows, alpha = D / (D + cov_rows - 1).  Limits: 3 <= P <= 32, P <= cov_rows <= 1024, D <= 128 and
+    P holdout + cov_rows complete rows.  Raises as pre_estimation_partial does; a local matrix that is not positive
+    definite raises numpy.linalg.LinAlgError naming the z indices.  The reference's route (BFGS over the D (D + 1) / 2
+    factor entries on the dense P D x P D Gaussian) is not taken."""
+    r = pre_estimate(x, Y, z, P=P, device=device, cov_rows=cov_rows, shrink=shrink, holdout=holdout)
+    return r["v_array"], r["L_tensor"], r["sigma2_err_log_array"]
+
+
 def pre_estimation_partial(x, Y, z, P=10, device=None):
     """code/pre_nmgp.py:102-125 -> (v_array (M,), L_tensor (D, D, M), sigma2_err_log_array (M,)) as numpy.
 
@@ -99,7 +170,7 @@ def pre_estimation_partial(x, Y, z, P=10, device=None):
 
 def pre_estimation_all(x, Y, z, P=10):
     """code/pre_nmgp.py:64-100 also fits the coefficient factor per window; the reference stops in pdb inside its
-    loop (:89-90) and never returns.  Not provided."""
+    loop (:89-90) and never returns.  Not provided; pre_estimation_local gives per-window factors by another route."""
     raise NotImplementedError("pre_estimation_all is not provided: the reference's own version stops in a debugger; "
                               "use pre_estimation_partial")
 

@@ -949,6 +949,42 @@ int nmgp_pre_loglik_f64(const double* x, int64_t x_stride, const double* Yrot, i
                         const double* z, int64_t z_stride, int N, int D, int M, int P, const double* pars, int E,
                         double* nll, int32_t* flags, int32_t* neighbours, hipStream_t stream);
 
+/* The same search and evaluation on windows handed over as data (code/pre_nmgp.py:64-100: the coefficient factor
+ * differs from window to window, so every window has its own eigenbasis): xs[m * P + p] the window inputs,
+ * Yrot_loc[(m * P + p) * D + d] = (Y_loc V_m), mu[m * D + d] the eigenvalues of that window's B_m = V_m diag(mu_m)
+ * V_m^T.  The kernel body, the search, the flags and the results are those of the two entries above; a window with a
+ * non-finite input is flagged degenerate.  window_flags (optional, M): a window with a non-zero entry (the flags of
+ * nmgp_pre_local_factor_f64) is not fitted, its results are NaN and its flags that entry.  NMGP_ERR_PREEST_ARG before any launch when P is outside 3..32, D outside
+ * 1..128, M or E is negative, a required pointer is NULL or M P D passes 2^31 - 1.                              */
+int nmgp_pre_estimate_windows_f64(const double* xs, const double* Yrot_loc, const double* mu, int M, int D, int P,
+                                  const int32_t* window_flags, double* log_ell, double* log_s, double* nll,
+                                  int32_t* flags, double* box, hipStream_t stream);
+int nmgp_pre_loglik_windows_f64(const double* xs, const double* Yrot_loc, const double* mu, int M, int D, int P,
+                                const int32_t* window_flags, const double* pars, int E, double* nll, int32_t* flags,
+                                hipStream_t stream);
+
+/* Local coefficient factors around the inducing points, fused (csrc/prelocal.hip): what the reference's
+ * pre_estimation_all (code/pre_nmgp.py:64-100) set out to estimate per window, one workgroup per inducing point.
+ * The rows with a finite |x_n - z_m| are ordered by (|x_n - z_m|, n); the fit window is the first P rows (the window
+ * of nmgp_pre_estimate_f64), the covariance window the next cov_rows rows (holdout = 1) or the first cov_rows rows
+ * (holdout = 0).  B_local[m] = w (Y_w^T Y_w) + alpha B (D x D, symmetric bit for bit; Y_w the covariance rows, summed
+ * in ascending row order on the fp64 matrix cores; B (D x D, row stride ld_b) the global matrix), L[m] its lower
+ * Cholesky factor (upper triangle 0, no jitter).  Also written: neighbours[m * P + p] and cov_neighbours[m * cov_rows
+ * + c] in ascending row order, xs[m * P + p] and Yloc[(m * P + p) * D + d] the fit rows, flags[m]: 32 fewer than
+ * P holdout + cov_rows finite inputs (tables -1, the rest NaN), NMGP_PRE_FLAG_FACTOR a pivot of B_local[m] was not
+ * positive (L[m] is NaN; the other windows are unaffected).  The same call gives the same bits, and a window's bits
+ * do not depend on the other windows.  Returns NMGP_ERR_PRELOCAL_ARG before any launch when P is outside 3..32,
+ * D outside 1..128, cov_rows outside P..1024, P holdout + cov_rows > N, alpha outside [0, 1], w negative or not
+ * finite, holdout not 0 / 1, a pointer is NULL, a stride is below 1, ld_y or ld_b < D, or an element offset passes
+ * 2^31 - 1.                                                                                                  */
+#define NMGP_ERR_PRELOCAL_ARG (-69)
+#define NMGP_PRE_FLAG_FACTOR 64
+int nmgp_pre_local_factor_f64(const double* x, int64_t x_stride, const double* Y, int64_t ld_y, const double* B,
+                              int64_t ld_b, const double* z, int64_t z_stride, int N, int D, int M, int P,
+                              int cov_rows, int holdout, double w, double alpha, double* B_local, double* L,
+                              int32_t* neighbours, int32_t* cov_neighbours, double* xs, double* Yloc, int32_t* flags,
+                              hipStream_t stream);
+
 /* Whole-step HIP graphs (the reference runs its step eagerly, code/nmgp_dsvi.py:829-854; the build captures
  * noise -> forward -> backward -> Adam once and replays it).  Capture goes straight through the HIP runtime:
  * begin on `stream` (thread-local mode; other streams join through event waits and must join back before
